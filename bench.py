@@ -4,8 +4,17 @@ points/scalars per GPU) through the C-ABI of libgnark_mi355x.so, plus the
 secondary metrics the same BASELINE metric names (NTT Gelem/s at 2^24, Groth16
 prove time) on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--logn 20]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--logn 20] [--full] [--dump-outputs DIR]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
+
+A plain run sets up, warms up, times the K pipelined steps and prints the
+headline line (metric, value, ms_per_step, ...).  --full adds everything else:
+the synchronous latency MSMs and the accumulation kernel's roofline, the
+per-kernel averages, the secondaries (NTT, further MSMs, Groth16 proves with
+their oracle checks, N > 1: the sharded proves) and the CPU baselines;
+--no-secondary / --no-cpu-baseline trim a --full run.  --dump-outputs DIR writes
+the last timed step's result (the affine point gm_msm_wait hands the caller) as
+DIR/msm_affine.npy.
 
 Multi-GPU = the MSM sharded by splitting the point/scalar array across ranks
 (weak scaling: every rank holds a fixed 2^logn shard); each step every rank runs
@@ -67,7 +76,22 @@ def parse():
                     help="N>1: sharded Groth16 prove domain (BASELINE config 4; 0 = skip)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the synchronous latency / roofline, the secondaries and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's MSM result as DIR/msm_affine.npy (float64 u32 limbs)")
     return ap.parse_args()
+
+
+def dump_outputs(d, aff):
+    """The last timed step's result as the caller of gm_msm_wait receives it: the
+    gnark G1Affine (X, Y) bytes, Montgomery form, as their little-endian u32
+    limbs in float64 (exact).  The G1Jac triple handed back beside it is not
+    written: it is one of many representations of the same point and differs from
+    run to run of one build (measured; the affine point does not)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "msm_affine.npy"), np.frombuffer(aff, "<u4").astype(np.float64))
 
 
 def load_pmc_traffic(name):
@@ -157,10 +181,10 @@ def main():
     def finish(pend):
         """Host tail of one step: this rank's partial, plus (N > 1) the all-gather
         of every rank's 96-B partial and the host adds -- the full sharded MSM."""
-        local = pend.wait()[0]
+        local, aff = pend.wait()
         if dist is None:
-            return local
-        return gm.reduce_partials("bn254", False, gm.allgather_partial(local))
+            return local, aff
+        return gm.reduce_partials("bn254", False, gm.allgather_partial(local)), None
 
     def run(k):
         """k MSMs, pipelined PIPE_DEPTH deep (gm_msm_async, one stream per MSM):
@@ -178,30 +202,40 @@ def main():
             r = finish(pend.pop(0))
         return r
 
-    run(args.warmup)
-    # unpipelined latency of one MSM (synchronous gm_msm), for reference; its
-    # kernel timings give the accumulation's launch time with nothing beside it
-    ctx.profile_reset()
+    # the timed loop runs with the library's profile scopes on, so the warm-up
+    # does too: a scope's first use creates its events (measured: a 20-step line
+    # 3 % lower when the timed loop is the first profiled work; before --full
+    # existed the latency MSMs below, then part of every run, paid for that)
     ctx.profile(True)
-    t0 = time.perf_counter()
-    for _ in range(3):
-        step()
-    lat_ms = (time.perf_counter() - t0) / 3 * 1e3
+    run(args.warmup)
     ctx.profile(False)
-    # the accumulation's own execution: first wave start .. last wave end, stamped by
-    # its waves (msm_accum_g1_exec, csrc/runtime.hpp ProfScope::wave_stamp); the
-    # launch's event brackets (msm_accum_g1) also hold the time it waited for wave
-    # slots held by the other MSMs' kernels
-    iso_stats = ctx.profile_stats()
-    iso_ms, iso_cnt = iso_stats.get("msm_accum_g1_exec", (0.0, 0))
-    if not iso_cnt:
-        iso_ms, iso_cnt = iso_stats.get("msm_accum_g1", (0.0, 0))
-    iso_avg_ms = iso_ms / max(iso_cnt, 1)
+    lat_ms = iso_avg_ms = 0.0
+    if args.full:
+        # unpipelined latency of one MSM (synchronous gm_msm), for reference; its
+        # kernel timings give the accumulation's launch time with nothing beside it
+        ctx.profile_reset()
+        ctx.profile(True)
+        t0 = time.perf_counter()
+        for _ in range(3):
+            step()
+        lat_ms = (time.perf_counter() - t0) / 3 * 1e3
+        ctx.profile(False)
+        # the accumulation's own execution: first wave start .. last wave end, stamped by
+        # its waves (msm_accum_g1_exec, csrc/runtime.hpp ProfScope::wave_stamp); the
+        # launch's event brackets (msm_accum_g1) also hold the time it waited for wave
+        # slots held by the other MSMs' kernels
+        iso_stats = ctx.profile_stats()
+        iso_ms, iso_cnt = iso_stats.get("msm_accum_g1_exec", (0.0, 0))
+        if not iso_cnt:
+            iso_ms, iso_cnt = iso_stats.get("msm_accum_g1", (0.0, 0))
+        iso_avg_ms = iso_ms / max(iso_cnt, 1)
+    # profile scopes on in a plain run too: the headline is measured under the
+    # same conditions with and without --full
     ctx.profile_reset()
     ctx.profile(True)
     barrier()
     t0 = time.perf_counter()
-    res = run(args.steps)
+    res, res_aff = run(args.steps)
     barrier()
     dt = time.perf_counter() - t0
     ctx.profile(False)
@@ -213,7 +247,45 @@ def main():
     ms_per_step = dt * 1e3 / args.steps
     total_points = n * world
     value = total_points / (dt / args.steps) / 1e6
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res_aff or gm.jac_to_affine("bn254", False, res))
 
+    out = {
+        "metric": "BN254 G1 MSM Mpoints/s (2^%d points per GPU, sharded MSM)" % args.logn,
+        "value": round(value, 3),
+        "unit": "Mpoints/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u32 limbs (BN254 Fp/Fr Montgomery, integer)",
+        "data": "synthetic: uniform scalars, points [k_i]G1 (seeded)",
+        "config": {"workload": "BN254 G1 MSM 2^%d random points/scalars per GPU (BASELINE configs[1])" % args.logn,
+                   "points_per_gpu": n, "total_points": total_points, "parallelism": "msm-shard%d" % world},
+        "pipeline": ("steps pipelined %d deep (gm_msm_async / gm_msm_wait, one stream per MSM): the next steps' "
+                     "device work is queued before step i's host tail (N > 1: incl. the all-gather of partials and "
+                     "the host adds)" % PIPE_DEPTH),
+        "hip_hw_queues": {"value": _process_env("GPU_MAX_HW_QUEUES"),
+                          "set_by": "environment" if hwq_preset else "unset (HIP's default)"},
+    }
+    if args.full:
+        full_lines(out, args, ctx, gm, torch, dist, barrier, rank, world, n, stats, ms_per_step, lat_ms, iso_avg_ms,
+                   S, P, res)
+    if rank == 0:
+        print(json.dumps(out))
+    ctx.close()
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def full_lines(out, args, ctx, gm, torch, dist, barrier, rank, world, n, stats, ms_per_step, lat_ms, iso_avg_ms,
+               S, P, res):
+    """--full: the accumulation kernel's roofline and the per-kernel averages from
+    the timed loop's profile scopes, the synchronous latency, the secondaries and
+    the CPU baselines, added to the headline line `out`."""
     # ---- roofline of the dominant kernel (bucket accumulation) ------------------
     br_ms, br_cnt = stats.get("msm_accum_g1", (0.0, 0))
     bracket_avg_ms = br_ms / max(br_cnt, 1)
@@ -286,30 +358,10 @@ def main():
     }
     kernel_ms = {k: round(v[0] / max(v[1], 1), 4) for k, v in stats.items()}
 
-    out = {
-        "metric": "BN254 G1 MSM Mpoints/s (2^%d points per GPU, sharded MSM)" % args.logn,
-        "value": round(value, 3),
-        "unit": "Mpoints/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u32 limbs (BN254 Fp/Fr Montgomery, integer)",
-        "data": "synthetic: uniform scalars, points [k_i]G1 (seeded)",
-        "config": {"workload": "BN254 G1 MSM 2^%d random points/scalars per GPU (BASELINE configs[1])" % args.logn,
-                   "points_per_gpu": n, "total_points": total_points, "parallelism": "msm-shard%d" % world},
-        "roofline": roofline,
-        "kernel_avg_ms": kernel_ms,
-        "pipeline": ("steps pipelined %d deep (gm_msm_async / gm_msm_wait, one stream per MSM): the next steps' "
-                     "device work is queued before step i's host tail (N > 1: incl. the all-gather of partials and "
-                     "the host adds); latency_ms = one synchronous (N > 1: sharded) MSM" % PIPE_DEPTH),
-        "latency_ms": round(lat_ms, 4),
-        "hip_hw_queues": {"value": _process_env("GPU_MAX_HW_QUEUES"),
-                          "set_by": "environment" if hwq_preset else "unset (HIP's default)"},
-    }
+    out["roofline"] = roofline
+    out["kernel_avg_ms"] = kernel_ms
+    out["pipeline"] += "; latency_ms = one synchronous (N > 1: sharded) MSM"
+    out["latency_ms"] = round(lat_ms, 4)
 
     if rank == 0 and not args.no_secondary and world == 1:
         out["secondary"] = secondary(ctx, gm, args)
@@ -332,11 +384,6 @@ def main():
         barrier()
     if rank == 0 and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(S, P, n, res)
-    if rank == 0:
-        print(json.dumps(out))
-    ctx.close()
-    if dist is not None:
-        dist.destroy_process_group()
 
 
 def _process_env(name):

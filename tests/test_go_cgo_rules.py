@@ -298,12 +298,37 @@ def test_names_used_are_declared_in_the_same_tag_set():
                         f"{pkg}/{f} {sorted(tags)}: calls method {name}, not declared in this tag set"
 
 
+def diff_old_side(text):
+    """{path: text} of the files a unified diff patches, as far as the diff
+    itself shows them: every hunk's old side (context and removed lines) at its
+    line numbers, empty lines in between and nothing after the last hunk."""
+    files, cur, pos = {}, None, 0
+    for line in text.splitlines(True):
+        if line.startswith("--- a/"):
+            cur = files.setdefault(line[6:].split("\t")[0].strip(), {})
+        elif line.startswith("+++ "):
+            continue
+        elif line.startswith("@@"):
+            pos = int(re.match(r"@@ -(\d+)", line).group(1))
+        elif line[0] in " -":
+            cur[pos] = line[1:]
+            pos += 1
+    return {p: "".join(ls.get(i, "\n") for i in range(1, max(ls) + 1)) for p, ls in files.items()}
+
+
+def write_tree(root, files):
+    for rel, src in files.items():
+        (root / os.path.dirname(rel)).mkdir(parents=True, exist_ok=True)
+        (root / rel).write_text(src)
+
+
 def test_levelhook_diff_applies_to_the_reference_solver(tmp_path):
     """integration/go/solver_levelhook.diff (the csolver.WithLevelHook the
     staged prover needs) is a real patch: `patch --dry-run` applies it cleanly
     to the reference's constraint/solver/options.go and constraint/{bn254,
     bls12-377}/solver.go (copied to a temp dir; nothing under /root/reference
-    is written)."""
+    is written).  Without a reference checkout the same is checked on the old
+    side of the patched files that the diff itself holds (diff_old_side)."""
     import shutil
     import subprocess
     import pytest
@@ -313,11 +338,17 @@ def test_levelhook_diff_applies_to_the_reference_solver(tmp_path):
     assert "func WithLevelHook(h LevelHook) Option" in text
     assert text.count("solver.levelDone(level)") == 4  # both branches of run(), both curves
     files = ["constraint/solver/options.go", "constraint/bn254/solver.go", "constraint/bls12-377/solver.go"]
-    if not all(os.path.exists(os.path.join(ref, f)) for f in files) or shutil.which("patch") is None:
-        pytest.skip("reference checkout or patch(1) not available")
-    for f in files:
-        (tmp_path / os.path.dirname(f)).mkdir(parents=True, exist_ok=True)
-        shutil.copy(os.path.join(ref, f), tmp_path / f)
+    if shutil.which("patch") is None:
+        pytest.skip("patch(1) not available")
+    have_ref = all(os.path.exists(os.path.join(ref, f)) for f in files)
+    old = diff_old_side(text)
+    assert sorted(old) == sorted(files)
+    if have_ref:
+        for f in files:
+            (tmp_path / os.path.dirname(f)).mkdir(parents=True, exist_ok=True)
+            shutil.copy(os.path.join(ref, f), tmp_path / f)
+    else:
+        write_tree(tmp_path, old)
     r = subprocess.run(["patch", "-p1", "--dry-run", "-F0", "-i", diff], cwd=tmp_path, capture_output=True, text=True)
     assert r.returncode == 0 and "FAILED" not in r.stdout and "fuzz" not in r.stdout, r.stdout + r.stderr
     # the staged prover uses exactly the hook type the patch declares
@@ -344,13 +375,20 @@ def test_levelhook_diff_applies_to_the_reference_solver(tmp_path):
     mk = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mk)
     import difflib
-    regen = []
-    for rel, fn in (("constraint/bn254/solver.go", mk.patch_solver), ("constraint/bls12-377/solver.go",
-                                                                     mk.patch_solver),
-                    ("constraint/solver/options.go", mk.patch_options)):
-        a = open(os.path.join(ref, rel)).read()
-        regen += difflib.unified_diff(a.splitlines(True), fn(a).splitlines(True), "a/" + rel, "b/" + rel, n=3)
-    assert "".join(regen) == text
+    gens = (("constraint/bn254/solver.go", mk.patch_solver), ("constraint/bls12-377/solver.go", mk.patch_solver),
+            ("constraint/solver/options.go", mk.patch_options))
+    if have_ref:
+        regen = []
+        for rel, fn in gens:
+            a = open(os.path.join(ref, rel)).read()
+            regen += difflib.unified_diff(a.splitlines(True), fn(a).splitlines(True), "a/" + rel, "b/" + rel, n=3)
+        assert "".join(regen) == text
+    else:
+        # the generator's edits of the old side are exactly what the diff applies to it
+        r = subprocess.run(["patch", "-p1", "-F0", "-i", diff], cwd=tmp_path, capture_output=True, text=True)
+        assert r.returncode == 0, r.stdout + r.stderr
+        for rel, fn in gens:
+            assert (tmp_path / rel).read_text() == fn(old[rel]), rel
 
 
 def test_prove_diff_applies_to_the_reference_plonk_prover(tmp_path):
@@ -359,11 +397,16 @@ def test_prove_diff_applies_to_the_reference_plonk_prover(tmp_path):
     import pytest
     ref = "/root/reference/backend/plonk/bls12-377/prove.go"
     diff = os.path.join(GO_DIR, "plonk_bls12377", "prove.go.diff")
-    if not os.path.exists(ref) or shutil.which("patch") is None:
-        pytest.skip("reference checkout or patch(1) not available")
-    dst = tmp_path / "backend/plonk/bls12-377"
-    dst.mkdir(parents=True)
-    shutil.copy(ref, dst / "prove.go")
+    if shutil.which("patch") is None:
+        pytest.skip("patch(1) not available")
+    if os.path.exists(ref):
+        dst = tmp_path / "backend/plonk/bls12-377"
+        dst.mkdir(parents=True)
+        shutil.copy(ref, dst / "prove.go")
+    else:  # the old side of prove.go as far as the diff holds it
+        old = diff_old_side(open(diff).read())
+        assert list(old) == ["backend/plonk/bls12-377/prove.go"]
+        write_tree(tmp_path, old)
     r = subprocess.run(["patch", "-p1", "--dry-run", "-F0", "-i", diff], cwd=tmp_path, capture_output=True, text=True)
     assert r.returncode == 0 and "FAILED" not in r.stdout and "fuzz" not in r.stdout, r.stdout + r.stderr
 
