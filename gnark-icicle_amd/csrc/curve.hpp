@@ -9,6 +9,12 @@
 //   add        (add-2008-s)   12M + 2S
 //   double     (dbl-2008-s-1)  6M + 3S
 // (hyperelliptic.org EFD, "g1p/auto-shortw-xyzz").  Infinity is ZZ = 0.
+//
+// Stored G1 buckets and partial sums are lazily reduced, not canonical: x < 8p,
+// y, zz, zzz < 2p with normalised limbs, as xyzz_add_aff_lz leaves them.
+// xyzz_add_lz takes such operands; xyzz_canon_raw is their canonical form, first
+// applied by k_msm_seg (msm_impl.hpp, "Storage contract"; -6.9 % VALU
+// instructions per accumulation wave at 2^20, profiles/raw_bucket_emit_pmc.txt).
 #pragma once
 #include "field.hpp"
 
@@ -111,7 +117,11 @@ GM_DEV void xyzz_add_aff(XYZZ<F>& a, const Affine<F>& p) {
 
 // Lazily reduced a += (neg ? -p : p) for G1 buckets (see field.hpp "Lazily
 // reduced arithmetic").  Invariants on a: x < 8p, y < 4p, zz < 2p, zzz < 2p
-// (canonical values qualify); p canonical.  Every product below has inputs with
+// (canonical values qualify); p canonical.  What it leaves is tighter in y: < 1.5p
+// after an add, <= p after the copy of a first entry, canonical after a doubling
+// -- so an accumulator is stored as it stands, with no canonical pass: x < 8p,
+// y, zz, zzz < 2p is the contract of stored buckets (msm_impl.hpp, "Storage
+// contract") that xyzz_add_lz accepts.  Every product below has inputs with
 // ab <= 100 p^2 (largest: P^2 with P < 10p).  zz is never a non-zero multiple
 // of p (zz * PP with PP != 0 mod p), so fe_is_zero(zz) still tests infinity.
 // The digit sign is applied to S2 = y zzz (carry-free 2p - S2) rather than to y,
@@ -125,7 +135,9 @@ GM_DEV void xyzz_add_aff_lz(XYZZ<Fe<P>>& a, const Affine<Fe<P>>& p, bool neg) {
   if (aff_is_inf(p)) return;
   if (xyzz_is_inf(a)) {
     a.x = p.x;
-    a.y = neg ? fe_neg(p.y) : p.y;
+    // p.y is canonical, so p - y is one borrow pass (fe_neg: that plus a masked
+    // add-p pass); limbs normalised for fe_negk_cf<5> at the next entry
+    a.y = neg ? fe_pminus(p.y) : p.y;
     a.zz = fe_one<P>();
     a.zzz = fe_one<P>();
     return;
@@ -204,17 +216,6 @@ GM_DEV XYZZ<Fe2<P, BETA>> xyzz_canon_lz(const XYZZ<Fe2<P, BETA>>& a) {
   return {c(a.x), c(a.y), c(a.zz), c(a.zzz)};
 }
 
-// canonical form of a lazily accumulated bucket
-template <class P>
-GM_DEV XYZZ<Fe<P>> xyzz_canon_lz(const XYZZ<Fe<P>>& a) {
-  XYZZ<Fe<P>> r;
-  r.x = fe_canon<3>(a.x);
-  r.y = fe_canon<2>(a.y);
-  r.zz = fe_canon<1>(a.zz);
-  r.zzz = fe_canon<1>(a.zzz);
-  return r;
-}
-
 // 2*a (dbl-2008-s-1, a = 0).  Infinity maps to infinity (ZZ3 = V*0).
 template <class F>
 GM_DEV XYZZ<F> xyzz_dbl(const XYZZ<F>& a) {
@@ -263,9 +264,22 @@ template <class P>
 GM_DEV XYZZ<Fe<P>> xyzz_canon2(const XYZZ<Fe<P>>& a) {
   return {fe_canon<1>(a.x), fe_canon<1>(a.y), fe_canon<1>(a.zz), fe_canon<1>(a.zzz)};
 }
+// canonical form of a stored G1 bucket / part / running sum: x < 8p, the rest < 2p
+template <class P>
+GM_DEV XYZZ<Fe<P>> xyzz_canon_raw(const XYZZ<Fe<P>>& a) {
+  return {fe_canon<3>(a.x), fe_canon<1>(a.y), fe_canon<1>(a.zz), fe_canon<1>(a.zzz)};
+}
 
-// Lazily reduced a + b (G1 bucket fixup and reduction): coordinates < 2p in and
-// out (canonical values qualify).  Product inputs stay below 4p x 4p = 16 p^2.
+// Lazily reduced a + b (G1 bucket fixup and reduction).  In: x < 8p, y, zz,
+// zzz < 2p on either operand -- what the accumulation stores (msm_impl.hpp,
+// "Storage contract"); canonical values qualify.  Out: every coordinate < 2p,
+// except that an operand is returned as it came when the other one is infinity.
+// x enters only through U1 = a.x b.zz and U2 = b.x a.zz: 8p 2p = 16 p^2, so
+// U < 16 p^2 / R' + p < 1.13p with R' > 128 p (BN254: R' / p = 2^261 / p > 169;
+// BLS12-377, 14 limbs: R' / p = 2^406 / p > 2^28), and the 64-bit columns hold
+// 2 N 2^58 as for any normalised operands: 8p keeps every limb below 2^29 (its top limb
+// is 8 p_top + carry < 2^26 for BN254 and < 8 for BLS12-377, whose p ends at limb 12).
+// Every other product input pair stays below 4p x 4p = 16 p^2.
 // A lazily reduced zz is a non-zero residue unless the point is infinity (set
 // canonically), so fe_is_zero(zz) still tests infinity.
 template <class P>
@@ -280,7 +294,7 @@ GM_DEV XYZZ<Fe<P>> xyzz_add_lz(const XYZZ<Fe<P>>& a, const XYZZ<Fe<P>>& b) {
   const F Pd = fe_sub_lz<2>(U2, U1);  // < 4p
   const F R = fe_sub_lz<2>(S2, S1);   // < 4p
   if (fe_is_zero_lz<4>(Pd)) {
-    if (fe_is_zero_lz<4>(R)) return xyzz_dbl(xyzz_canon2(a));
+    if (fe_is_zero_lz<4>(R)) return xyzz_dbl(xyzz_canon_raw(a));
     return xyzz_inf<F>();
   }
   const F PP = fe_sqr_lz(Pd);  // < 2p

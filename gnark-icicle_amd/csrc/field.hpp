@@ -477,6 +477,20 @@ GM_DEV Fe<P> fe_sub_lz(const Fe<P>& a, const Fe<P>& b) {
   }
   return r;
 }
+// p - a for a <= p with normalised limbs: one borrow pass, no sign test.  The
+// result, in [0, p] (p itself for a = 0), has normalised limbs.
+template <class P>
+GM_DEV Fe<P> fe_pminus(const Fe<P>& a) {
+  Fe<P> r;
+  int32_t borrow = 0;
+#pragma unroll
+  for (int i = 0; i < P::N; i++) {
+    const int32_t d = (int32_t)P::p(i) - (int32_t)a.v[i] + borrow;
+    borrow = d >> RADIX;
+    r.v[i] = i == P::N - 1 ? (uint32_t)d : ((uint32_t)d & LIMB_MASK);
+  }
+  return r;
+}
 // a - K p if a >= K p
 template <int K, class P>
 GM_DEV void fe_reduce_k(Fe<P>& a) {

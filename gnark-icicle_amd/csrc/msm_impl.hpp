@@ -15,6 +15,11 @@
 //                       (sign applied on load); buckets cut by slice edges go to
 //                       part_first / part_last and are merged by k_msm_fixup
 //                       (k_msm_fix_tree + k_msm_fixup_long for spans > FIX_SERIAL).
+//                       Buckets and parts are stored as the lazy add leaves them,
+//                       each once ("Storage contract" at LazyAcc): at the 2^20
+//                       bench shape 51,930 VALU instructions per wave against
+//                       55,793 with a canonical emit inside the loop, 146 MB
+//                       written against 205 (profiles/raw_bucket_emit_pmc.txt).
 //   4. k_msm_seg        bucket reduction level 1: running sums over segments of
 //                       L buckets;  k_msm_bitsum: LDS bit-sum trees up to one node
 //                       per window;  k_msm_export: nodes -> gnark words.
@@ -466,7 +471,29 @@ GM_DEV PackedPt<PW> load_packed_pt(const uint32_t* __restrict__ src) {
 // edges go to part_first[t] / part_last[t] and are merged by k_msm_fixup.
 // Skewed scalar distributions (one huge bucket) therefore cost the same as
 // uniform ones in this phase.
-// Buckets accumulate lazily reduced (xyzz_add_aff_lz), canonical on emit.
+//
+// Storage contract of `buckets`, `part_first` and `part_last` (G1, Fe<P>): the
+// lazily reduced accumulator is stored as it stands, with no canonical pass --
+//   x < 8p,  y < 2p,  zz < 2p,  zzz < 2p,  limbs normalised (the top limb keeps
+//   the excess), infinity as xyzz_inf() (zz = 0 exactly).
+// The fixup kernels store their sums under the same contract; xyzz_add_lz takes
+// such operands (curve.hpp), and k_msm_seg makes its running sums canonical
+// (xyzz_canon_raw) when it stores the nodes -- the first canonical pass of a
+// bucket's life.  (Before: seven fe_reduce_k passes and two offsets loads per
+// bucket boundary, inside the divergent region of the hot loop.)
+// G2 buckets (lane pairs, pair_fp2.hpp) are stored canonical: the raw emit there
+// measured within noise (3.78-3.80 -> 3.77-3.80 ms at 2^20) and put the BN254
+// pair kernel, at its 168-VGPR cap, into scratch (profiles/raw_bucket_emit_ab.txt).
+//
+// Which of the three arrays a run of equal keys goes to is decided by the sorted
+// keys alone: a run that neither begins at the slice start nor ends at the slice
+// end is whole.  The first run continues the previous slice iff
+// keys[start - 1] == keys[start]; the last run continues into the next slice
+// iff keys[end] == its key (end < Mv).  The fixup's sum of a cut bucket is
+// part_last[t0] + part_first[t0+1] + ... + part_first[t1], so a run that
+// continues the previous slice is stored in part_first[t] only (also when it
+// fills the whole slice and goes on), and a run that begins in this slice and
+// goes on past its end in part_last[t] only.
 template <class F>
 struct LazyAcc {
   static constexpr bool on = false;
@@ -475,7 +502,6 @@ struct LazyAcc {
     if (neg) p.y = fe_neg(p.y);
     xyzz_add_aff(a, p);
   }
-  GM_DEV static XYZZ<F> canon(const XYZZ<F>& a) { return a; }
 };
 template <class P>
 struct LazyAcc<Fe<P>> {
@@ -486,33 +512,7 @@ struct LazyAcc<Fe<P>> {
     // per-column chains, bench line +1.7 % (profiles/r05an_strict_chain_ab.txt)
     xyzz_add_aff_lz<P, CH ? 2 : 0>(a, p, neg);
   }
-  GM_DEV static XYZZ<Fe<P>> canon(const XYZZ<Fe<P>>& a) { return xyzz_canon_lz(a); }
 };
-template <class P, int B>
-struct LazyAcc<Fe2<P, B>> {
-  static constexpr bool on = true;
-  template <bool CH = false>
-  GM_DEV static void add(XYZZ<Fe2<P, B>>& a, Affine<Fe2<P, B>> p, bool neg) {
-    if (neg) p.y = fe_neg(p.y);
-    xyzz_add_aff_lz(a, p);
-  }
-  GM_DEV static XYZZ<Fe2<P, B>> canon(const XYZZ<Fe2<P, B>>& a) { return xyzz_canon_lz(a); }
-};
-
-template <class F>
-GM_DEV void accum_emit(uint32_t b, const XYZZ<F>& acc_raw, bool is_first, bool is_last, uint32_t start,
-                       uint32_t end, uint32_t t, const uint32_t* __restrict__ offsets,
-                       XYZZ<F>* __restrict__ buckets, XYZZ<F>* __restrict__ part_first,
-                       XYZZ<F>* __restrict__ part_last) {
-  const XYZZ<F> acc = LazyAcc<F>::canon(acc_raw);
-  const uint32_t bs = offsets[b], be = offsets[b + 1];
-  if (bs >= start && be <= end) {
-    buckets[b] = acc;
-  } else {
-    if (is_first) part_first[t] = acc;
-    if (is_last) part_last[t] = acc;
-  }
-}
 
 // Profiled launches (ProfScope::wave_stamp): lane 0 of a wave stamps the wall
 // clock on entry (atomicMin) and after the body, where the wave's lanes have
@@ -554,9 +554,12 @@ GM_DEV void accum_seg_body_v4(const uint32_t* __restrict__ points, uint32_t n, c
   const uint32_t end = min(start + K, Mv);
   uint4 kg = *reinterpret_cast<const uint4*>(keys + start);
   uint4 vg = *reinterpret_cast<const uint4*>(vals + start);
-  bool first = true;
   XYZZ<F> acc = xyzz_inf<F>();
   uint32_t cur = kg.x;
+  // the two slice edges (see "Storage contract" above): does the first run of
+  // keys continue the previous slice, and which key follows the slice
+  bool cont_prev = start > 0 && keys[start - 1] == cur;
+  const uint32_t key_after = end < Mv ? keys[end] : 0xffffffffu;  // no bucket has this index
   uint32_t v = vg.x;
   if ((v & 0x7fffffffu) >= n) {
     atomicOr(err, 2u);
@@ -588,9 +591,9 @@ GM_DEV void accum_seg_body_v4(const uint32_t* __restrict__ points, uint32_t n, c
       if (PREFETCH) Pn = load_packed_pt<PW>(points + (size_t)(vn & 0x7fffffffu) * PW);
     }
     if (!PREFETCH) P = load_packed_pt<PW>(points + (size_t)(v & 0x7fffffffu) * PW);
-    if (k != cur) {
-      accum_emit(cur, acc, first, false, start, end, t, offsets, buckets, part_first, part_last);
-      first = false;
+    if (k != cur) {  // the run of `cur` ends inside the slice
+      *(cont_prev ? part_first + t : buckets + cur) = acc;
+      cont_prev = false;
       acc = xyzz_inf<F>();
       cur = k;
     }
@@ -599,7 +602,7 @@ GM_DEV void accum_seg_body_v4(const uint32_t* __restrict__ points, uint32_t n, c
     v = vn;
     if (PREFETCH) P = Pn;
   }
-  accum_emit(cur, acc, first, true, start, end, t, offsets, buckets, part_first, part_last);
+  *(cont_prev ? part_first + t : (key_after == cur ? part_last + t : buckets + cur)) = acc;
 }
 
 // BN254 G1: one strict mad chain per product inside the add (r05; the split-
@@ -683,16 +686,24 @@ template <class F>
 constexpr bool kOneLane = !PairSel<F>::ok;
 
 // Full adds of the fixup / reduction kernels: lazily reduced for G1
-// (xyzz_add_lz, canonical on store), canonical xyzz_add otherwise.
+// (xyzz_add_lz), canonical xyzz_add otherwise.  A G1 sum is < 2p in every
+// coordinate, or one of the operands unchanged when the other is infinity.  So:
+//   the fixup kernels store sums of raw buckets / parts as they are (the
+//     storage contract of the accumulation above holds for them);
+//   canon   a sum whose operands may be raw (k_msm_seg: a segment with a single
+//     non-empty bucket hands that bucket through): x < 8p;
+//   canon2  a sum of canonical operands (k_msm_bitsum's nodes): < 2p.
 template <class F>
 struct FullAdd {
   GM_DEV static XYZZ<F> add(const XYZZ<F>& a, const XYZZ<F>& b) { return xyzz_add(a, b); }
   GM_DEV static XYZZ<F> canon(const XYZZ<F>& a) { return a; }
+  GM_DEV static XYZZ<F> canon2(const XYZZ<F>& a) { return a; }
 };
 template <class P>
 struct FullAdd<Fe<P>> {
   GM_DEV static XYZZ<Fe<P>> add(const XYZZ<Fe<P>>& a, const XYZZ<Fe<P>>& b) { return xyzz_add_lz(a, b); }
-  GM_DEV static XYZZ<Fe<P>> canon(const XYZZ<Fe<P>>& a) { return xyzz_canon2(a); }
+  GM_DEV static XYZZ<Fe<P>> canon(const XYZZ<Fe<P>>& a) { return xyzz_canon_raw(a); }
+  GM_DEV static XYZZ<Fe<P>> canon2(const XYZZ<Fe<P>>& a) { return xyzz_canon2(a); }
 };
 
 // Merge the partial sums of buckets cut by slice edges.  Bucket b spans slices
@@ -721,7 +732,7 @@ __global__ void __launch_bounds__(128) k_msm_fixup(const uint32_t* __restrict__ 
   }
   XYZZ<F> acc = part_last[t0];
   for (uint32_t t = t0 + 1; t <= t1; t++) acc = FullAdd<F>::add(acc, part_first[t]);
-  buckets[b] = FullAdd<F>::canon(acc);
+  buckets[b] = acc;
 }
 
 // The same merge, one thread per slice edge t >= 1: the bucket holding entry t K
@@ -756,7 +767,7 @@ __global__ void __launch_bounds__(128) k_msm_fixup_edge(const uint32_t* __restri
   }
   XYZZ<F> acc = part_last[t0];
   for (uint32_t u = t; u <= t1; u++) acc = FullAdd<F>::add(acc, part_first[u]);
-  buckets[b] = FullAdd<F>::canon(acc);
+  buckets[b] = acc;
 }
 // One level d of the pairwise tree over part_first[t0+1 .. t1] of every long span.
 template <class F>
@@ -771,7 +782,7 @@ __global__ void __launch_bounds__(128) k_msm_fix_tree(const uint32_t* __restrict
   if (t1 - t0 <= FIX_SERIAL || t <= t0) return;
   const uint32_t rel = t - (t0 + 1), len = t1 - t0, step = 1u << d;
   if ((rel & ((step << 1) - 1)) == 0 && rel + step < len)
-    part_first[t] = FullAdd<F>::canon(FullAdd<F>::add(part_first[t], part_first[t + step]));
+    part_first[t] = FullAdd<F>::add(part_first[t], part_first[t + step]);
 }
 
 template <class F>
@@ -785,7 +796,7 @@ __global__ void __launch_bounds__(128) k_msm_fixup_long(const uint32_t* __restri
   if (be == bs) return;
   const uint32_t t0 = bs / K, t1 = (be - 1) / K;
   if (t1 - t0 <= FIX_SERIAL) return;
-  buckets[b] = FullAdd<F>::canon(FullAdd<F>::add(part_last[t0], part_first[t0 + 1]));
+  buckets[b] = FullAdd<F>::add(part_last[t0], part_first[t0 + 1]);
 }
 
 // ---------------------------------------------------------------------------
@@ -814,6 +825,8 @@ constexpr uint32_t BS_THREADS = 256;
 // A bucket with no entries (offsets[b] == offsets[b + 1]) was never written by
 // the accumulation or the fixup: it reads as infinity here, so the buckets need no
 // clearing before the accumulation (a 1 GB memset per plain 2^24 MSM).
+// Non-empty buckets arrive under the storage contract of the accumulation (raw,
+// x < 8p); the running sums are made canonical when they are stored as nodes.
 template <class F>
 __global__ void __launch_bounds__(128) k_msm_seg(const XYZZ<F>* __restrict__ buckets,
                                                  const uint32_t* __restrict__ offsets, uint32_t nb, uint32_t L,
@@ -860,7 +873,7 @@ __global__ void __launch_bounds__(BS_THREADS) k_msm_bitsum(const XYZZ<F>* __rest
       const uint32_t t = threadIdx.x;
       if (t < tasks) {
         const uint32_t p = t / qc, q = t % qc, base = p * 2 * child;
-        r0 = (q + 1 < qc) ? FullAdd<F>::canon(FullAdd<F>::add(X[base + q], X[base + child + q])) : X[base + child];
+        r0 = (q + 1 < qc) ? FullAdd<F>::canon2(FullAdd<F>::add(X[base + q], X[base + child + q])) : X[base + child];
         s0 = base + q;
       }
     }
@@ -868,7 +881,7 @@ __global__ void __launch_bounds__(BS_THREADS) k_msm_bitsum(const XYZZ<F>* __rest
       const uint32_t t = threadIdx.x + blockDim.x;
       if (t < tasks) {
         const uint32_t p = t / qc, q = t % qc, base = p * 2 * child;
-        r1 = (q + 1 < qc) ? FullAdd<F>::canon(FullAdd<F>::add(X[base + q], X[base + child + q])) : X[base + child];
+        r1 = (q + 1 < qc) ? FullAdd<F>::canon2(FullAdd<F>::add(X[base + q], X[base + child + q])) : X[base + child];
         s1 = base + q;
       }
     }
