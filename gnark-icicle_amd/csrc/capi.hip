@@ -300,6 +300,13 @@ int gm_set_msm_glv(gm_ctx* ctx, int mode) {
   return GM_OK;
 }
 
+int gm_set_msm_piece_len(gm_ctx* ctx, int t) {
+  if (!ctx || t < 0 || t > (int)gm::PIECE_MAX_LEN) return GM_ERR_INVALID;
+  gm::CtxLock g(ctx);
+  ctx->msm_piece_len = t;
+  return GM_OK;
+}
+
 // ---- memory -----------------------------------------------------------------
 int gm_malloc(gm_ctx* ctx, size_t bytes, void** dev_out) {
   gm::CtxLock g(ctx);
@@ -369,6 +376,20 @@ int gm_msm(gm_ctx* ctx, int curve, int g2, const void* scalars_dev, const void* 
 }
 
 }  // extern "C"
+
+// Piece length of the G1 accumulation (MsmPlan, msm.hpp) for a plan of at most
+// M entries: the same size split as the G2 slice length K (msm_launch).  The
+// values are the measured ones (profiles/piece_plan_ab.txt).
+#ifndef GM_PIECE_LEN_SMALL
+#define GM_PIECE_LEN_SMALL 48
+#endif
+#ifndef GM_PIECE_LEN_LARGE
+#define GM_PIECE_LEN_LARGE 64
+#endif
+uint32_t gm::msm_piece_len(const gm_ctx* ctx, size_t M) {
+  if (ctx && ctx->msm_piece_len > 0) return (uint32_t)ctx->msm_piece_len;
+  return M <= (size_t(1) << 25) ? GM_PIECE_LEN_SMALL : GM_PIECE_LEN_LARGE;
+}
 
 bool gm::msm_glv_on(const gm_ctx* ctx, bool g2, size_t n) {
   if (ctx && ctx->msm_glv >= 0) return ctx->msm_glv != 0;

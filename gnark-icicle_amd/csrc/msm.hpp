@@ -81,14 +81,33 @@ struct MsmPlan {
   uint32_t* keys = nullptr;     // sorted bucket keys (window-major bucket index), offsets[total] entries
   uint32_t* vals = nullptr;     // point index | sign << 31
   uint32_t* offsets = nullptr;  // total + 1 bucket start offsets
+  // Piece plan (G1 accumulation, msm_piece_plan): every non-empty bucket of len
+  // entries is cut into ceil(len / T) pieces of nearly equal length, and the
+  // pieces are counting-sorted by length, longest first, so that the lanes of a
+  // wave run the same number of adds.  A piece is {first entry, length,
+  // destination, 0}: the destination is the bucket itself when the bucket is one
+  // piece, else PIECE_PART | part slot; a cut bucket b owns the contiguous part
+  // slots pbase[b] .. pbase[b] + ceil(len / T).
+  uint32_t T = 0;                   // piece length cap (0: no piece plan, G2-only plans)
+  size_t max_pieces = 0, max_parts = 0;  // bounds for allocation and launch
+  uint4* pieces = nullptr;          // pcount[0] descriptors
+  uint32_t* pcount = nullptr;       // [0] pieces, [1] part slots
+  uint32_t* pbase = nullptr;        // per bucket: first part slot (cut buckets only)
+  uint32_t* partb = nullptr;        // per part slot: its bucket
 };
+constexpr uint32_t PIECE_PART = 0x80000000u;
+constexpr uint32_t PIECE_MAX_LEN = 128;  // length classes of the counting sort
+// Piece length for a plan of M entries at most (gm_set_msm_piece_len overrides it)
+uint32_t msm_piece_len(const gm_ctx* ctx, size_t M);
+// Builds the piece plan of `plan` (offsets must be queued on ctx->stream).
+int msm_piece_plan(gm_ctx* ctx, Arena& arena, MsmPlan& plan, uint32_t T);
 // glv (plain layout, BN254 and BLS12-377): each scalar k is split
 // k = k1 + k2 lambda with |k1|, |k2| < 2^127, over 2n points
 // [P_0..P_{n-1}, phi(P_0)..phi(P_{n-1})] (msm_device_launch builds them): half
 // the windows, so half the buckets to reduce, for the same number of bucket adds.
 template <class C>
 int msm_plan(gm_ctx* ctx, Arena& arena, const void* scalars_dev, size_t n, const MsmPrecomp* pre,
-             MsmPlan& plan, bool glv = false);
+             MsmPlan& plan, bool glv = false, bool pieces = true);
 // GLV for an MSM of n points on ctx: the context's setting (gm_set_msm_glv)
 // or, by default, on for n up to 2^21 (G1 and G2)
 bool msm_glv_on(const gm_ctx* ctx, bool g2, size_t n);
@@ -106,6 +125,10 @@ struct MsmTail {
   uint32_t wn = 0;  // first narrow (c - 1 bit) window of the plan (window_geom)
   const uint32_t* keys = nullptr;
   const uint32_t* offsets = nullptr;
+  // G1: the plan's piece length and part tables; `pfirst` holds the part slots
+  uint32_t T = 0;
+  size_t max_parts = 0;
+  const uint32_t *pcount = nullptr, *pbase = nullptr, *partb = nullptr;
   void *buckets = nullptr, *pfirst = nullptr, *plast = nullptr, *nodes_a = nullptr, *nodes_b = nullptr;
   void *wsum = nullptr, *errw = nullptr;
   uint8_t* stage = nullptr;  // pinned readback: 16 B (error, max span) + the exported nodes

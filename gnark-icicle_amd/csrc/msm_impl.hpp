@@ -10,11 +10,15 @@
 //   2. k_msm_s2_*       (msm_sort.hip) each coarse bin -> its buckets: sorted
 //                       (bucket, point index | sign << 31) entries and the bucket
 //                       start offsets, written directly.
-//   3. k_msm_accum_seg  load-balanced slices of K sorted entries per thread:
-//                       lazily reduced XYZZ mixed adds of the gathered points
-//                       (sign applied on load); buckets cut by slice edges go to
-//                       part_first / part_last and are merged by k_msm_fixup
-//                       (k_msm_fix_tree + k_msm_fixup_long for spans > FIX_SERIAL).
+//   3. k_msm_accum_seg  G1: one lane per piece of the plan's piece plan (buckets
+//                       cut into ceil(len / T) pieces of nearly equal length,
+//                       sorted by length; k_msm_pp_* in msm_sort.hip): lazily
+//                       reduced XYZZ mixed adds of the gathered points (sign
+//                       applied on load), one store; the parts of a cut bucket lie
+//                       in contiguous slots and are merged by k_msm_fixup
+//                       (k_msm_fix_tree + k_msm_fixup_long above FIX_SERIAL adds).
+//                       G2: slices of K sorted entries per lane pair, buckets cut
+//                       by slice edges in part_first / part_last (pair_fp2.hpp).
 //                       Buckets and parts are stored as the lazy add leaves them,
 //                       each once ("Storage contract" at LazyAcc): at the 2^20
 //                       bench shape 51,930 VALU instructions per wave against
@@ -465,35 +469,29 @@ GM_DEV PackedPt<PW> load_packed_pt(const uint32_t* __restrict__ src) {
   return r;
 }
 
-// Load-balanced accumulation over the sorted entry list: thread t owns entries
-// [t*K, t*K+K).  A bucket whose whole range lies in the thread's slice is
-// written straight to `buckets`; the (at most two) buckets cut by the slice
-// edges go to part_first[t] / part_last[t] and are merged by k_msm_fixup.
-// Skewed scalar distributions (one huge bucket) therefore cost the same as
-// uniform ones in this phase.
+// Accumulation over the plan's pieces (MsmPlan, msm.hpp): lane t owns piece t,
+// at most T consecutive sorted entries of ONE bucket.  A bucket that is a single
+// piece is written straight to `buckets`; the pieces of a cut bucket go to its
+// contiguous part slots and are merged by k_msm_fixup.  Every piece is at most T
+// entries whatever the bucket, so skewed scalar distributions (one huge bucket)
+// cost the same as uniform ones in this phase, and the pieces are sorted by
+// length, so the lanes of a wave run the same number of adds.
 //
-// Storage contract of `buckets`, `part_first` and `part_last` (G1, Fe<P>): the
-// lazily reduced accumulator is stored as it stands, with no canonical pass --
+// Storage contract of `buckets` and `parts` (G1, Fe<P>): the lazily reduced
+// accumulator is stored as it stands, with no canonical pass --
 //   x < 8p,  y < 2p,  zz < 2p,  zzz < 2p,  limbs normalised (the top limb keeps
 //   the excess), infinity as xyzz_inf() (zz = 0 exactly).
 // The fixup kernels store their sums under the same contract; xyzz_add_lz takes
 // such operands (curve.hpp), and k_msm_seg makes its running sums canonical
 // (xyzz_canon_raw) when it stores the nodes -- the first canonical pass of a
-// bucket's life.  (Before: seven fe_reduce_k passes and two offsets loads per
-// bucket boundary, inside the divergent region of the hot loop.)
-// G2 buckets (lane pairs, pair_fp2.hpp) are stored canonical: the raw emit there
-// measured within noise (3.78-3.80 -> 3.77-3.80 ms at 2^20) and put the BN254
-// pair kernel, at its 168-VGPR cap, into scratch (profiles/raw_bucket_emit_ab.txt).
-//
-// Which of the three arrays a run of equal keys goes to is decided by the sorted
-// keys alone: a run that neither begins at the slice start nor ends at the slice
-// end is whole.  The first run continues the previous slice iff
-// keys[start - 1] == keys[start]; the last run continues into the next slice
-// iff keys[end] == its key (end < Mv).  The fixup's sum of a cut bucket is
-// part_last[t0] + part_first[t0+1] + ... + part_first[t1], so a run that
-// continues the previous slice is stored in part_first[t] only (also when it
-// fills the whole slice and goes on), and a run that begins in this slice and
-// goes on past its end in part_last[t] only.
+// bucket's life.  Every non-empty bucket is written exactly once by the
+// accumulation (one piece) or by the fixup (cut buckets); empty buckets are
+// never written and never read (k_msm_seg).
+// G2 buckets (lane pairs, pair_fp2.hpp) stay on the slice grid -- thread t owns
+// entries [t*K, t*K+K), buckets cut by slice edges go to part_first / part_last
+// -- and are stored canonical: the raw emit there measured within noise
+// (3.78-3.80 -> 3.77-3.80 ms at 2^20) and put the BN254 pair kernel, at its
+// 168-VGPR cap, into scratch (profiles/raw_bucket_emit_ab.txt).
 template <class F>
 struct LazyAcc {
   static constexpr bool on = false;
@@ -530,79 +528,82 @@ GM_DEV void wave_stamp_end(unsigned long long* stamp) {
     atomicMax(stamp + (blockIdx.x & 63) * 32 + 1, (unsigned long long)wall_clock64());
 }
 
-// G1 accumulation body: keys and values arrive four entries per 16-byte load
-// instead of one 4-byte load per entry (r05).  A thread's slice is K
-// consecutive entries and consecutive lanes are K entries apart, so each 4-byte
-// load touched one cache line per lane and the line rarely survived in L1 until
-// the lane's next entry (rocprofv3 FETCH_SIZE of the accumulation: 2.8 GB per
-// 2^20 MSM against 1.1 GB of 64-byte point gathers, profiles/r05f_*).  The next
-// group's keys / values are loaded at the last entry of the current group.  (Pinning
-// the point's four 16-byte loads with an empty asm, against the vectoriser's
-// unaligned x2 / x3 / x4 split, costs 32 B of scratch per lane.)  Reads past
-// the thread's last entry stay inside the allocation: slices start at multiples
-// of K (K % 4 == 0) and the workspace arena rounds every allocation to 256 bytes.
+// Four consecutive entry values in one 16-byte load.  A piece starts at any
+// entry, so the address is only 4-byte aligned; gfx950 takes a global dwordx4
+// load at that alignment.
+struct __attribute__((packed, aligned(4))) EntryQuad {
+  uint32_t x, y, z, w;
+};
+GM_DEV uint4 load_entry_quad(const uint32_t* __restrict__ p) {
+  const EntryQuad q = *reinterpret_cast<const EntryQuad*>(p);
+  return make_uint4(q.x, q.y, q.z, q.w);
+}
+
+// Entry q -> q + 1 of a piece: shifts the value group, loads the next group at a
+// group boundary (its latency overlaps entry q's add), bounds-checks entry
+// q + 1 and, with PREFETCH, loads its point.  false: bad point index (err = 2).
+template <int PW, bool PREFETCH>
+GM_DEV bool accum_next(const uint32_t* __restrict__ points, uint32_t n, const uint32_t* __restrict__ vp,
+                       uint32_t len, uint32_t q, uint4& vg, uint32_t& vn, PackedPt<PW>& Pn,
+                       uint32_t* __restrict__ err) {
+  if ((q & 3) == 3) {
+    if (q + 1 < len) vg = load_entry_quad(vp + q + 1);
+  } else {
+    vg = make_uint4(vg.y, vg.z, vg.w, vg.w);
+  }
+  vn = vg.x;  // entry q + 1 (when q + 1 < len)
+  if (q + 1 < len) {
+    if ((vn & 0x7fffffffu) >= n) {
+      atomicOr(err, 2u);
+      return false;
+    }
+    if (PREFETCH) Pn = load_packed_pt<PW>(points + (size_t)(vn & 0x7fffffffu) * PW);
+  }
+  return true;
+}
+
+// G1 accumulation body: len lazy adds into an accumulator that starts at
+// infinity, then ONE raw store.  Every lane of a wave is at the first entry of
+// its piece in the same step, q = 0, so the copy branch of xyzz_add_aff_lz
+// (fe_pminus for a negated entry; an infinity point leaves infinity) is taken by
+// the whole wave there and the add is skipped (s_cbranch_execz); it stays
+// inside the loop because hoisted in front of it the BN254 kernel needs 128
+// VGPRs and 28 bytes of scratch against 120 and none.  No keys are read: the
+// bucket is the descriptor's, which is read again for the store rather than
+// held in a register.  Values arrive four entries per 16-byte load (r05: 4-byte
+// loads touched one cache line per lane per entry).  Reads past the piece's last
+// entry stay inside `vals`, which is allocated 16 bytes longer than its entries
+// (msm_plan).  A wave whose lanes hold two length classes loops to its longest
+// piece.
 template <class F, bool CH, bool PREFETCH = false>
-GM_DEV void accum_seg_body_v4(const uint32_t* __restrict__ points, uint32_t n, const uint32_t* __restrict__ keys,
-                              const uint32_t* __restrict__ vals, const uint32_t* __restrict__ offsets,
-                              uint32_t total, uint32_t K, XYZZ<F>* __restrict__ buckets,
-                              XYZZ<F>* __restrict__ part_first, XYZZ<F>* __restrict__ part_last,
-                              uint32_t* __restrict__ err) {
+GM_DEV void accum_piece_body(const uint32_t* __restrict__ points, uint32_t n, const uint32_t* __restrict__ vals,
+                             const uint4* __restrict__ pieces, const uint32_t* __restrict__ pcount,
+                             XYZZ<F>* __restrict__ buckets, XYZZ<F>* __restrict__ parts,
+                             uint32_t* __restrict__ err) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t Mv = offsets[total];  // valid (non-zero-digit) entries
-  const uint32_t start = t * K;
-  if (start >= Mv) return;
-  const uint32_t end = min(start + K, Mv);
-  uint4 kg = *reinterpret_cast<const uint4*>(keys + start);
-  uint4 vg = *reinterpret_cast<const uint4*>(vals + start);
-  XYZZ<F> acc = xyzz_inf<F>();
-  uint32_t cur = kg.x;
-  // the two slice edges (see "Storage contract" above): does the first run of
-  // keys continue the previous slice, and which key follows the slice
-  bool cont_prev = start > 0 && keys[start - 1] == cur;
-  const uint32_t key_after = end < Mv ? keys[end] : 0xffffffffu;  // no bucket has this index
+  if (t >= pcount[0]) return;
+  const uint32_t* vp = vals + pieces[t].x;  // {first entry, length >= 1, destination, -}
+  const uint32_t len = pieces[t].y;
+  uint4 vg = load_entry_quad(vp);
   uint32_t v = vg.x;
   if ((v & 0x7fffffffu) >= n) {
     atomicOr(err, 2u);
     return;
   }
   constexpr int PW = 2 * Coord<F>::WORDS;  // u32 words per packed point
-  PackedPt<PW> P;
+  PackedPt<PW> P, Pn;
   if (PREFETCH) P = load_packed_pt<PW>(points + (size_t)(v & 0x7fffffffu) * PW);
-  for (uint32_t q = start; q < end; q++) {
-    const uint32_t k = kg.x;
-    // next entry: shift the group; at a group boundary load the next group (its
-    // latency overlaps this entry's add)
-    if (((q - start) & 3) == 3) {
-      if (q + 1 < end) {
-        kg = *reinterpret_cast<const uint4*>(keys + q + 1);
-        vg = *reinterpret_cast<const uint4*>(vals + q + 1);
-      }
-    } else {
-      kg = make_uint4(kg.y, kg.z, kg.w, kg.w);
-      vg = make_uint4(vg.y, vg.z, vg.w, vg.w);
-    }
-    const uint32_t vn = vg.x;  // entry q + 1 (when q + 1 < end)
-    PackedPt<PW> Pn;
-    if (q + 1 < end) {
-      if ((vn & 0x7fffffffu) >= n) {
-        atomicOr(err, 2u);
-        return;
-      }
-      if (PREFETCH) Pn = load_packed_pt<PW>(points + (size_t)(vn & 0x7fffffffu) * PW);
-    }
+  XYZZ<F> acc = xyzz_inf<F>();
+  for (uint32_t q = 0; q < len; q++) {
+    uint32_t vn;
+    if (!accum_next<PW, PREFETCH>(points, n, vp, len, q, vg, vn, Pn, err)) return;
     if (!PREFETCH) P = load_packed_pt<PW>(points + (size_t)(v & 0x7fffffffu) * PW);
-    if (k != cur) {  // the run of `cur` ends inside the slice
-      *(cont_prev ? part_first + t : buckets + cur) = acc;
-      cont_prev = false;
-      acc = xyzz_inf<F>();
-      cur = k;
-    }
-    const Affine<F> A = load_affine_packed<F>(P.w);
-    LazyAcc<F>::template add<CH>(acc, A, (v >> 31) != 0);
+    LazyAcc<F>::template add<CH>(acc, load_affine_packed<F>(P.w), (v >> 31) != 0);
     v = vn;
     if (PREFETCH) P = Pn;
   }
-  *(cont_prev ? part_first + t : (key_after == cur ? part_last + t : buckets + cur)) = acc;
+  const uint32_t dst = pieces[t].z;
+  *((dst & PIECE_PART) ? parts + (dst & ~PIECE_PART) : buckets + dst) = acc;
 }
 
 // BN254 G1: one strict mad chain per product inside the add (r05; the split-
@@ -612,13 +613,12 @@ GM_DEV void accum_seg_body_v4(const uint32_t* __restrict__ points, uint32_t n, c
 // chains slowed the one-to-two-wave reduction kernels (r04h, r05ax).
 template <class F>
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4)))
-k_msm_accum_seg_ch(const uint32_t* __restrict__ points, uint32_t n, const uint32_t* __restrict__ keys,
-                   const uint32_t* __restrict__ vals, const uint32_t* __restrict__ offsets, uint32_t total,
-                   uint32_t K, XYZZ<F>* __restrict__ buckets, XYZZ<F>* __restrict__ part_first,
-                   XYZZ<F>* __restrict__ part_last, uint32_t* __restrict__ err,
+k_msm_accum_seg_ch(const uint32_t* __restrict__ points, uint32_t n, const uint32_t* __restrict__ vals,
+                   const uint4* __restrict__ pieces, const uint32_t* __restrict__ pcount,
+                   XYZZ<F>* __restrict__ buckets, XYZZ<F>* __restrict__ parts, uint32_t* __restrict__ err,
                    unsigned long long* __restrict__ stamp) {
   wave_stamp_begin(stamp);
-  accum_seg_body_v4<F, true>(points, n, keys, vals, offsets, total, K, buckets, part_first, part_last, err);
+  accum_piece_body<F, true>(points, n, vals, pieces, pcount, buckets, parts, err);
   wave_stamp_end(stamp);
 }
 // Four waves fit the 9-limb fields only: BLS12-377's 14-limb add spills 216
@@ -635,16 +635,15 @@ struct AccumW4<Fe<P>> {
 // (BLS12-377 G1: two waves per SIMD).
 template <class F>
 __global__ void __launch_bounds__(128) k_msm_accum_seg_pf4(const uint32_t* __restrict__ points, uint32_t n,
-                                                           const uint32_t* __restrict__ keys,
                                                            const uint32_t* __restrict__ vals,
-                                                           const uint32_t* __restrict__ offsets, uint32_t total,
-                                                           uint32_t K, XYZZ<F>* __restrict__ buckets,
-                                                           XYZZ<F>* __restrict__ part_first,
-                                                           XYZZ<F>* __restrict__ part_last,
+                                                           const uint4* __restrict__ pieces,
+                                                           const uint32_t* __restrict__ pcount,
+                                                           XYZZ<F>* __restrict__ buckets,
+                                                           XYZZ<F>* __restrict__ parts,
                                                            uint32_t* __restrict__ err,
                                                            unsigned long long* __restrict__ stamp) {
   wave_stamp_begin(stamp);
-  accum_seg_body_v4<F, false, true>(points, n, keys, vals, offsets, total, K, buckets, part_first, part_last, err);
+  accum_piece_body<F, false, true>(points, n, vals, pieces, pcount, buckets, parts, err);
   wave_stamp_end(stamp);
 }
 // G1 accumulation kernel of a field
@@ -706,97 +705,65 @@ struct FullAdd<Fe<P>> {
   GM_DEV static XYZZ<Fe<P>> canon2(const XYZZ<Fe<P>>& a) { return xyzz_canon2(a); }
 };
 
-// Merge the partial sums of buckets cut by slice edges.  Bucket b spans slices
-// t0..t1 and its sum is part_last[t0] + part_first[t0+1] + ... + part_first[t1].
-// Spans up to FIX_SERIAL slices are summed by one thread; longer spans (a huge
-// bucket: skewed witness values, or the nearly empty top window of a scalar
-// field much narrower than W*c bits) are tree-reduced in place over part_first
-// by k_msm_fix_tree levels -- depth log2(span) adds instead of span serial adds.
+// Merge the parts of the cut buckets (G1; the lane-pair kernels of G2 merge
+// slice parts, pair_fp2.hpp).  Bucket b of len > T entries has p = ceil(len / T)
+// parts in the contiguous slots parts[pbase[b] .. pbase[b] + p), and its sum is
+// their sum in slot order.  Up to FIX_SERIAL adds (p - 1) are done by one thread;
+// buckets with more parts (a huge bucket: skewed witness values, or the nearly
+// empty top window of a scalar field much narrower than W*c bits) report
+// p - 1 through `maxspan` and are tree-reduced in place over their slots by
+// k_msm_fix_tree levels -- depth log2(p) adds instead of p serial ones.
 constexpr uint32_t FIX_SERIAL = 8;
 
 template <class F>
 __global__ void __launch_bounds__(128) k_msm_fixup(const uint32_t* __restrict__ offsets, uint32_t total,
-                                                   uint32_t K, XYZZ<F>* __restrict__ buckets,
-                                                   const XYZZ<F>* __restrict__ part_first,
-                                                   const XYZZ<F>* __restrict__ part_last,
+                                                   uint32_t T, XYZZ<F>* __restrict__ buckets,
+                                                   const XYZZ<F>* __restrict__ parts,
+                                                   const uint32_t* __restrict__ pbase,
                                                    uint32_t* __restrict__ maxspan) {
   const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= total) return;
-  const uint32_t bs = offsets[b], be = offsets[b + 1];
-  if (be == bs) return;
-  const uint32_t t0 = bs / K, t1 = (be - 1) / K;
-  if (t0 == t1) return;
-  if (t1 - t0 > FIX_SERIAL) {
-    atomicMax(maxspan, t1 - t0);
+  const uint32_t len = offsets[b + 1] - offsets[b];
+  if (len <= T) return;  // empty, or written whole by the accumulation
+  const uint32_t p = (len + T - 1) / T;
+  if (p - 1 > FIX_SERIAL) {
+    atomicMax(maxspan, p - 1);
     return;
   }
-  XYZZ<F> acc = part_last[t0];
-  for (uint32_t t = t0 + 1; t <= t1; t++) acc = FullAdd<F>::add(acc, part_first[t]);
+  const XYZZ<F>* q = parts + pbase[b];
+  XYZZ<F> acc = q[0];
+  for (uint32_t i = 1; i < p; i++) acc = FullAdd<F>::add(acc, q[i]);
   buckets[b] = acc;
 }
 
-// The same merge, one thread per slice edge t >= 1: the bucket holding entry t K
-// is cut by the edge when it starts before it, and the thread of its first edge
-// (t = t0 + 1) merges its parts -- the same adds in the same order.  Used when
-// buckets are shorter than a slice (M < K * buckets: the plain-key Groth16 2^24
-// MSMs, ~32 entries per bucket at K = 64): per bucket, a wave then mixes cut and
-// whole buckets and half its lanes idle through the add, while nearly every
-// edge cuts a bucket once.  Buckets longer than a slice are cut by one to three
-// edges each, so per edge the lanes idle instead: 2^24 plain 148.2 -> 147.3 ms,
-// precomputed (~96 entries per bucket) 137.5 -> 140.8 ms, 2^20 G1 (64 per bucket
-// at K = 32) fixup 0.11 -> 0.175 ms (profiles/r06g_fixup_edge_ab.txt).
+// One level d of the pairwise tree over the part slots of every long bucket:
+// one thread per slot (partb: the slot's bucket).
 template <class F>
-__global__ void __launch_bounds__(128) k_msm_fixup_edge(const uint32_t* __restrict__ keys,
-                                                        const uint32_t* __restrict__ offsets, uint32_t total,
-                                                        uint32_t K, uint32_t nslices,
-                                                        XYZZ<F>* __restrict__ buckets,
-                                                        const XYZZ<F>* __restrict__ part_first,
-                                                        const XYZZ<F>* __restrict__ part_last,
-                                                        uint32_t* __restrict__ maxspan) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x + 1;
-  if (t >= nslices) return;
-  const size_t q = (size_t)t * K;  // first entry of slice t
-  if (q >= offsets[total]) return;
-  const uint32_t b = keys[q];
-  const uint32_t bs = offsets[b];
-  if (bs >= q || bs / K != t - 1) return;  // not cut by this edge, or not its first edge
-  const uint32_t t0 = t - 1, t1 = (offsets[b + 1] - 1) / K;
-  if (t1 - t0 > FIX_SERIAL) {
-    atomicMax(maxspan, t1 - t0);
-    return;
-  }
-  XYZZ<F> acc = part_last[t0];
-  for (uint32_t u = t; u <= t1; u++) acc = FullAdd<F>::add(acc, part_first[u]);
-  buckets[b] = acc;
-}
-// One level d of the pairwise tree over part_first[t0+1 .. t1] of every long span.
-template <class F>
-__global__ void __launch_bounds__(128) k_msm_fix_tree(const uint32_t* __restrict__ keys,
-                                                      const uint32_t* __restrict__ offsets, uint32_t total,
-                                                      uint32_t K, uint32_t nslices, uint32_t d,
-                                                      XYZZ<F>* __restrict__ part_first) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= nslices || (size_t)t * K >= offsets[total]) return;
-  const uint32_t b = keys[(size_t)t * K];
-  const uint32_t t0 = offsets[b] / K, t1 = (offsets[b + 1] - 1) / K;
-  if (t1 - t0 <= FIX_SERIAL || t <= t0) return;
-  const uint32_t rel = t - (t0 + 1), len = t1 - t0, step = 1u << d;
-  if ((rel & ((step << 1) - 1)) == 0 && rel + step < len)
-    part_first[t] = FullAdd<F>::add(part_first[t], part_first[t + step]);
+__global__ void __launch_bounds__(128) k_msm_fix_tree(const uint32_t* __restrict__ offsets, uint32_t T,
+                                                      const uint32_t* __restrict__ pcount,
+                                                      const uint32_t* __restrict__ pbase,
+                                                      const uint32_t* __restrict__ partb, uint32_t d,
+                                                      XYZZ<F>* __restrict__ parts) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= pcount[1]) return;
+  const uint32_t b = partb[s];
+  const uint32_t p = (offsets[b + 1] - offsets[b] + T - 1) / T;
+  if (p - 1 <= FIX_SERIAL) return;
+  const uint32_t rel = s - pbase[b], step = 1u << d;
+  if ((rel & ((step << 1) - 1)) == 0 && rel + step < p) parts[s] = FullAdd<F>::add(parts[s], parts[s + step]);
 }
 
+// after the tree levels the first slot of a long bucket holds its sum
 template <class F>
 __global__ void __launch_bounds__(128) k_msm_fixup_long(const uint32_t* __restrict__ offsets, uint32_t total,
-                                                        uint32_t K, XYZZ<F>* __restrict__ buckets,
-                                                        const XYZZ<F>* __restrict__ part_first,
-                                                        const XYZZ<F>* __restrict__ part_last) {
+                                                        uint32_t T, XYZZ<F>* __restrict__ buckets,
+                                                        const XYZZ<F>* __restrict__ parts,
+                                                        const uint32_t* __restrict__ pbase) {
   const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= total) return;
-  const uint32_t bs = offsets[b], be = offsets[b + 1];
-  if (be == bs) return;
-  const uint32_t t0 = bs / K, t1 = (be - 1) / K;
-  if (t1 - t0 <= FIX_SERIAL) return;
-  buckets[b] = FullAdd<F>::add(part_last[t0], part_first[t0 + 1]);
+  const uint32_t len = offsets[b + 1] - offsets[b];
+  if (len <= T || (len + T - 1) / T - 1 <= FIX_SERIAL) return;
+  buckets[b] = parts[pbase[b]];
 }
 
 // ---------------------------------------------------------------------------
@@ -933,7 +900,7 @@ static int choose_window(size_t n, int bits) {
 // Keys, sort and bucket offsets for one scalar vector (see MsmPlan).
 template <class C>
 int msm_plan(gm_ctx* ctx, Arena& arena, const void* scalars_dev, size_t n, const MsmPrecomp* pre,
-             MsmPlan& plan, bool glv) {
+             MsmPlan& plan, bool glv, bool pieces) {
   hipStream_t st = ctx->stream;
   plan = MsmPlan();
   plan.n = n;
@@ -1015,7 +982,7 @@ int msm_plan(gm_ctx* ctx, Arena& arena, const void* scalars_dev, size_t n, const
   int rc;
   DevBuf dig, keys_out, vals_out, offsets, scount;
   if ((rc = dig.alloc(arena, sizeof(uint32_t) * M)) || (rc = keys_out.alloc(arena, sizeof(uint32_t) * M)) ||
-      (rc = vals_out.alloc(arena, sizeof(uint32_t) * M)) ||
+      (rc = vals_out.alloc(arena, sizeof(uint32_t) * M + 16)) ||  // + 16: accum_piece_body's group loads
       (rc = offsets.alloc(arena, sizeof(uint32_t) * ((size_t)plan.total + 1))) ||
       (rc = scount.alloc(arena, sizeof(uint32_t) * sg.NS)))
     return rc;
@@ -1058,6 +1025,10 @@ int msm_plan(gm_ctx* ctx, Arena& arena, const void* scalars_dev, size_t n, const
   plan.keys = keys_out.as<uint32_t>();
   plan.vals = vals_out.as<uint32_t>();
   plan.offsets = offsets.as<uint32_t>();
+  if (pieces) {
+    ProfScope ps(ctx, "msm_piece_plan");
+    if ((rc = msm_piece_plan(ctx, arena, plan, msm_piece_len(ctx, M)))) return rc;
+  }
   return GM_OK;
 }
 
@@ -1123,9 +1094,9 @@ template <class C, bool G2>
 int msm_fix_long(gm_ctx* ctx, MsmTail& t, uint32_t maxspan) {
   using DF = typename GroupSel<C, G2>::DF;
   hipStream_t st = ctx->stream;
-  const size_t nslices = (t.M + t.K - 1) / t.K;
   if constexpr (PairSel<DF>::ok) {
     {
+      const size_t nslices = (t.M + t.K - 1) / t.K;
       for (uint32_t d = 0; (1u << d) < maxspan; d++)
         hipLaunchKernelGGL(PairSel<DF>::fix_tree(), dim3(blocks_for(2 * nslices, 128)), dim3(128), 0, st, t.keys,
                            t.offsets, t.total, t.K, (uint32_t)nslices, d, (uint32_t*)t.pfirst, FIX_SERIAL);
@@ -1136,12 +1107,12 @@ int msm_fix_long(gm_ctx* ctx, MsmTail& t, uint32_t maxspan) {
       return GM_OK;
     }
   }
-  if constexpr (kOneLane<DF>) {
-    for (uint32_t d = 0; (1u << d) < maxspan; d++)
-      hipLaunchKernelGGL(k_msm_fix_tree<DF>, dim3(blocks_for(nslices, 128)), dim3(128), 0, st, t.keys, t.offsets,
-                         t.total, t.K, (uint32_t)nslices, d, (XYZZ<DF>*)t.pfirst);
+  if constexpr (kOneLane<DF>) {  // maxspan = parts - 1 of the longest bucket
+    for (uint32_t d = 0; (1u << d) <= maxspan; d++)
+      hipLaunchKernelGGL(k_msm_fix_tree<DF>, dim3(blocks_for(t.max_parts, 128)), dim3(128), 0, st, t.offsets, t.T,
+                         t.pcount, t.pbase, t.partb, d, (XYZZ<DF>*)t.pfirst);
     hipLaunchKernelGGL(k_msm_fixup_long<DF>, dim3(blocks_for(t.total, 128)), dim3(128), 0, st, t.offsets, t.total,
-                       t.K, (XYZZ<DF>*)t.buckets, (const XYZZ<DF>*)t.pfirst, (const XYZZ<DF>*)t.plast);
+                       t.T, (XYZZ<DF>*)t.buckets, (const XYZZ<DF>*)t.pfirst, t.pbase);
   }
   GM_HIP(hipGetLastError());
   return GM_OK;
@@ -1194,28 +1165,38 @@ int msm_launch(gm_ctx* ctx, Arena& arena, const MsmPlan& plan, const void* point
   while (Lwant < 32 && (size_t)t.Wr * t.nb / (2 * Lwant) >= (size_t(1) << 17)) Lwant *= 2;
   t.L = t.nb >= Lwant ? Lwant : t.nb;
   t.nseg = t.nb / t.L;
-  // Entries per accumulation thread.  64 by default; 24 for G1 MSMs of at most
-  // 2^25 entries (the 2^20 GLV bench MSM: 2^24 entries = 4,096 waves at 64, one
-  // round of four waves per SIMD, so the slowest waves set the time; at 32 the
-  // accumulation alone drops 1.38-1.43 -> 1.34 ms and the pipelined MSM loop gains
-  // 4-7 %, profiles/r04ae_slice_sweep.txt; with the ordered accumulations, 24
-  // gives shorter block rounds, so the next MSM's sort kernels find wave slots
-  // sooner: 641 -> 649 Mpoints/s same box, r06ai_slice_ab.txt).  Larger MSMs keep 64 (Groth16 2^24:
-  // 156.9 vs 159.3 ms at 32).  The long-span bound FIX_SERIAL * K stays above the
-  // fullest uniform bucket (64 entries at 2^20).  K % 4 == 0: the accumulation
-  // loads keys / values four entries at a time.  (K = 128 for the Groth16 2^24
-  // MSMs: within noise, profiles/r06d_g16_k128_ab.txt.)
-  t.K = !G2 && plan.M <= (size_t(1) << 25) ? 24u : 64u;
+  // G2: entries per accumulation lane pair (slice length), 64; K % 4 == 0 (keys /
+  // values arrive four entries per load), and the long-span bound FIX_SERIAL * K
+  // stays above the fullest uniform bucket.  (128 for the Groth16 2^24 MSMs:
+  // within noise, profiles/r06d_g16_k128_ab.txt.)  G1 runs on the plan's pieces of
+  // at most T entries instead (MsmPlan; T from msm_piece_len, sweep in
+  // profiles/piece_plan_ab.txt; the slice grid's K = 24 / 32 / 64 sweeps for G1 are
+  // in r04ae_slice_sweep.txt and r06ai_slice_ab.txt).
+  t.K = 64u;
+  if (!G2) {
+    if (!plan.T || !plan.pieces) {
+      set_error("msm: the plan has no piece plan (built for G2 only)");
+      return GM_ERR_INVALID;
+    }
+    t.T = plan.T;
+    t.max_parts = plan.max_parts;
+    t.pcount = plan.pcount;
+    t.pbase = plan.pbase;
+    t.partb = plan.partb;
+  }
   int rc;
   constexpr int WORDS = Coord<DF>::WORDS;  // u32 words of one gnark-layout coordinate
   static_assert(sizeof(HF) == 4 * WORDS, "host/device layout mismatch");
-  const size_t nslices = (t.M + t.K - 1) / t.K;
+  // part buffers: G2 one part_first / part_last per slice; G1 the cut buckets'
+  // part slots (in pfirst)
+  const size_t nslices = G2 ? (t.M + t.K - 1) / t.K : plan.max_parts;
   DevBuf buckets, nodes_a, nodes_b, wsum, errw, pfirst, plast;
   if ((rc = errw.alloc(arena, 16)) || (rc = buckets.alloc(arena, sizeof(XYZZ<DF>) * (size_t)t.total)) ||
       (rc = nodes_a.alloc(arena, sizeof(XYZZ<DF>) * 2 * (size_t)t.Wr * t.nseg)) ||
       (rc = nodes_b.alloc(arena, sizeof(XYZZ<DF>) * 2 * (size_t)t.Wr * t.nseg)) ||
       (rc = wsum.alloc(arena, sizeof(uint32_t) * 4 * WORDS * t.Wr * (2 + t.c))) ||
-      (rc = pfirst.alloc(arena, sizeof(XYZZ<DF>) * nslices)) || (rc = plast.alloc(arena, sizeof(XYZZ<DF>) * nslices)))
+      (rc = pfirst.alloc(arena, sizeof(XYZZ<DF>) * nslices)) ||
+      (rc = plast.alloc(arena, G2 ? sizeof(XYZZ<DF>) * nslices : 16)))
     return rc;
   t.buckets = buckets.p;
   t.nodes_a = nodes_a.p;
@@ -1245,37 +1226,32 @@ int msm_launch(gm_ctx* ctx, Arena& arena, const MsmPlan& plan, const void* point
                             plan.vals, plan.offsets, t.total, t.K, buckets.as<uint32_t>(), pfirst.as<uint32_t>(),
                             plast.as<uint32_t>(), errw.as<uint32_t>());
     } else {
-      hipExtLaunchKernelGGL(g1_accum_kernel<DF>(), dim3(blocks_for(nslices, 128)), dim3(128), 0, st, ps.a, ps.b, 0,
-                            reinterpret_cast<const uint32_t*>(points_internal), (uint32_t)plan.npts, plan.keys,
-                            plan.vals, plan.offsets, t.total, t.K, buckets.as<XYZZ<DF>>(), pfirst.as<XYZZ<DF>>(),
-                            plast.as<XYZZ<DF>>(), errw.as<uint32_t>(), ps.wave_stamp("msm_accum_g1_exec"));
+      hipExtLaunchKernelGGL(g1_accum_kernel<DF>(), dim3(blocks_for(plan.max_pieces, 128)), dim3(128), 0, st, ps.a,
+                            ps.b, 0, reinterpret_cast<const uint32_t*>(points_internal), (uint32_t)plan.npts,
+                            plan.vals, plan.pieces, plan.pcount, buckets.as<XYZZ<DF>>(), pfirst.as<XYZZ<DF>>(),
+                            errw.as<uint32_t>(), ps.wave_stamp("msm_accum_g1_exec"));
     }
   }
   {
     ProfScope ps(ctx, "msm_fixup");
-    if (plan.M < (size_t)t.K * t.total) {  // buckets shorter than a slice: per edge
-      if (nslices > 1) {
-        if constexpr (PairSel<DF>::ok)
+    if constexpr (PairSel<DF>::ok) {
+      if (plan.M < (size_t)t.K * t.total) {  // buckets shorter than a slice: per edge (pair_fp2.hpp)
+        if (nslices > 1)
           hipLaunchKernelGGL(PairSel<DF>::fixup_edge(), dim3(blocks_for(2 * (nslices - 1), 128)), dim3(128), 0, st,
                              plan.keys, plan.offsets, t.total, t.K, (uint32_t)nslices, buckets.as<uint32_t>(),
                              pfirst.as<uint32_t>(), plast.as<uint32_t>(), errw.as<uint32_t>() + 1, FIX_SERIAL);
-        else
-          hipLaunchKernelGGL(k_msm_fixup_edge<DF>, dim3(blocks_for(nslices - 1, 128)), dim3(128), 0, st, plan.keys,
-                             plan.offsets, t.total, t.K, (uint32_t)nslices, buckets.as<XYZZ<DF>>(),
-                             pfirst.as<XYZZ<DF>>(), plast.as<XYZZ<DF>>(), errw.as<uint32_t>() + 1);
+      } else {
+        hipLaunchKernelGGL(PairSel<DF>::fixup(), dim3(blocks_for(2 * (size_t)t.total, 128)), dim3(128), 0, st,
+                           plan.offsets, t.total, t.K, buckets.as<uint32_t>(), pfirst.as<uint32_t>(),
+                           plast.as<uint32_t>(), errw.as<uint32_t>() + 1, FIX_SERIAL);
       }
-    } else if constexpr (PairSel<DF>::ok) {
-      hipLaunchKernelGGL(PairSel<DF>::fixup(), dim3(blocks_for(2 * (size_t)t.total, 128)), dim3(128), 0, st,
-                         plan.offsets, t.total, t.K, buckets.as<uint32_t>(), pfirst.as<uint32_t>(),
-                         plast.as<uint32_t>(), errw.as<uint32_t>() + 1, FIX_SERIAL);
-    } else {
+    } else if (plan.M > t.T) {  // no bucket can be cut otherwise
       hipLaunchKernelGGL(k_msm_fixup<DF>, dim3(blocks_for(t.total, 128)), dim3(128), 0, st, plan.offsets, t.total,
-                         t.K, buckets.as<XYZZ<DF>>(), pfirst.as<XYZZ<DF>>(), plast.as<XYZZ<DF>>(),
-                         errw.as<uint32_t>() + 1);
+                         t.T, buckets.as<XYZZ<DF>>(), pfirst.as<XYZZ<DF>>(), plan.pbase, errw.as<uint32_t>() + 1);
     }
   }
   // Bucket reduction, launched speculatively: buckets spanning more than
-  // FIX_SERIAL slices (skewed scalars) are only known once errw[1] (max span)
+  // FIX_SERIAL slices (G1: of more than FIX_SERIAL + 1 parts; skewed scalars) are only known once errw[1] (max span)
   // reaches the host, so the reduction is queued right away and redone after the
   // long-span fixup in that (rare) case.  Speculate only when uniform scalars
   // would give no long span: the fullest bucket is then a top-window digit
@@ -1294,7 +1270,7 @@ int msm_launch(gm_ctx* ctx, Arena& arena, const MsmPlan& plan, const void* point
       const double load = (double)plan.n / h;
       fullest = t.Wr == 1 ? fullest + load : std::max(fullest, load);
     }
-    if (fullest > 0.5 * FIX_SERIAL * t.K) {
+    if (fullest > 0.5 * FIX_SERIAL * (G2 ? t.K : t.T)) {
       uint8_t* pb;
       int pbi;
       if ((rc = tail_pinned_acquire(ctx, 16, &pb, &pbi))) return rc;
@@ -1412,7 +1388,7 @@ int msm_device_launch(gm_ctx* ctx, Arena& arena, const void* scalars_dev, const 
     pts = ipts.p;
   }
   MsmPlan plan;
-  if ((rc = msm_plan<C>(ctx, arena, scalars_dev, n, pre, plan, glv))) return rc;
+  if ((rc = msm_plan<C>(ctx, arena, scalars_dev, n, pre, plan, glv, !G2))) return rc;
   // the caller's scalars (digits) and gnark-layout points (conversion) are not
   // read past this point
   if (inputs_read) GM_HIP(hipEventRecord(inputs_read, ctx->stream));
@@ -1475,6 +1451,6 @@ int msm_precompute_points(gm_ctx* ctx, const void* gnark_points, size_t n, const
   template int msm_device<C, G2>(gm_ctx*, const void*, const void*, size_t,                    \
                                  typename GroupSel<C, G2>::HF (&)[3], bool, const MsmPrecomp*);
 #define GM_MSM_INSTANTIATE_PLAN(C) \
-  template int msm_plan<C>(gm_ctx*, Arena&, const void*, size_t, const MsmPrecomp*, MsmPlan&, bool);
+  template int msm_plan<C>(gm_ctx*, Arena&, const void*, size_t, const MsmPrecomp*, MsmPlan&, bool, bool);
 
 }  // namespace gm

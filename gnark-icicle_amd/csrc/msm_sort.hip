@@ -524,6 +524,191 @@ int msm_sort_digits(gm_ctx* ctx, Arena& arena, const SortGeom& g, size_t n, uint
   return GM_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Piece plan of the G1 accumulation (MsmPlan, msm.hpp): buckets cut into
+// ceil(len / T) pieces of nearly equal length, the pieces counting-sorted by
+// length, longest first.  Three small kernels over the bucket offsets:
+//   k_msm_pp_hist     pieces per length class (LDS histogram, then one global
+//                     atomic per class per block)
+//   k_msm_pp_scan     one block: class bases, longest class first; piece count
+//   k_msm_pp_scatter  the descriptors, the part slots of the cut buckets
+//                     (pbase, one global reservation per block) and the bucket
+//                     of every part slot.  A bucket of more than PP_COOP pieces
+//                     (skewed scalars) is written by the whole block.
+// The order of the pieces inside a class, and of the cut buckets' part ranges,
+// follows the atomics: the group law makes the result independent of it.
+// ---------------------------------------------------------------------------
+constexpr uint32_t PP_THREADS = 256, PP_PER = 2, PP_CLASSES = PIECE_MAX_LEN + 1, PP_COOP = 32, PP_BIG = 256;
+
+// bucket of len entries -> p pieces: r of q + 1 entries first, then p - r of q
+__device__ __forceinline__ void pp_split(uint32_t len, uint32_t T, uint32_t& p, uint32_t& q, uint32_t& r) {
+  p = (len + T - 1) / T;
+  q = len / p;
+  r = len - q * p;
+}
+__device__ __forceinline__ void pp_write(uint32_t b, uint32_t bs, uint32_t p, uint32_t q, uint32_t r, uint32_t i,
+                                         uint32_t s0, uint32_t s1, uint32_t pb, uint4* __restrict__ pieces,
+                                         uint32_t* __restrict__ partb) {
+  const bool big = i < r;
+  const uint32_t start = big ? bs + i * (q + 1) : bs + r * (q + 1) + (i - r) * q;
+  pieces[big ? s1 + i : s0 + (i - r)] = make_uint4(start, big ? q + 1 : q, p == 1 ? b : PIECE_PART | (pb + i), 0u);
+  if (p > 1) partb[pb + i] = b;
+}
+
+static __global__ void __launch_bounds__(PP_THREADS) k_msm_pp_hist(const uint32_t* __restrict__ offsets,
+                                                                   uint32_t total, uint32_t T,
+                                                                   uint32_t* __restrict__ hist) {
+  __shared__ uint32_t h[PP_CLASSES];
+  const uint32_t t = threadIdx.x;
+  if (t < PP_CLASSES) h[t] = 0;
+  __syncthreads();
+  for (uint32_t k = 0; k < PP_PER; k++) {
+    const uint32_t b = (blockIdx.x * PP_PER + k) * PP_THREADS + t;
+    if (b >= total) break;
+    const uint32_t len = offsets[b + 1] - offsets[b];
+    if (!len) continue;
+    uint32_t p, q, r;
+    pp_split(len, T, p, q, r);
+    atomicAdd(&h[q], p - r);
+    if (r) atomicAdd(&h[q + 1], r);
+  }
+  __syncthreads();
+  if (t < PP_CLASSES && h[t]) atomicAdd(&hist[t], h[t]);
+}
+
+// cursor[l] = pieces longer than l; pcount[0] = all pieces, pcount[1] = 0
+static __global__ void __launch_bounds__(PP_THREADS) k_msm_pp_scan(const uint32_t* __restrict__ hist,
+                                                                   uint32_t* __restrict__ cursor,
+                                                                   uint32_t* __restrict__ pcount) {
+  __shared__ uint32_t h[PP_CLASSES];
+  const uint32_t t = threadIdx.x;
+  if (t < PP_CLASSES) h[t] = hist[t];
+  __syncthreads();
+  if (t == 0) {
+    uint32_t run = 0;
+    for (int l = (int)PP_CLASSES - 1; l >= 0; l--) {
+      const uint32_t c = h[l];
+      h[l] = run;
+      run += c;
+    }
+    pcount[0] = run;
+    pcount[1] = 0;
+  }
+  __syncthreads();
+  if (t < PP_CLASSES) cursor[t] = h[t];
+}
+
+static __global__ void __launch_bounds__(PP_THREADS) k_msm_pp_scatter(const uint32_t* __restrict__ offsets,
+                                                                      uint32_t total, uint32_t T,
+                                                                      uint32_t* __restrict__ cursor,
+                                                                      uint32_t* __restrict__ pcount,
+                                                                      uint4* __restrict__ pieces,
+                                                                      uint32_t* __restrict__ pbase,
+                                                                      uint32_t* __restrict__ partb) {
+  __shared__ uint32_t cnt[PP_CLASSES], base[PP_CLASSES];
+  __shared__ uint32_t nparts, part0, nbig;
+  __shared__ uint32_t bigb[PP_BIG], bigs0[PP_BIG], bigs1[PP_BIG], bigpb[PP_BIG];
+  const uint32_t t = threadIdx.x;
+  if (t < PP_CLASSES) cnt[t] = 0;
+  if (t == 0) {
+    nparts = 0;
+    nbig = 0;
+  }
+  __syncthreads();
+  uint32_t loc[PP_PER];  // the bucket's first part slot inside the block
+#pragma unroll
+  for (uint32_t k = 0; k < PP_PER; k++) {
+    const uint32_t b = (blockIdx.x * PP_PER + k) * PP_THREADS + t;
+    loc[k] = 0;
+    if (b >= total) continue;
+    const uint32_t len = offsets[b + 1] - offsets[b];
+    if (!len) continue;
+    uint32_t p, q, r;
+    pp_split(len, T, p, q, r);
+    atomicAdd(&cnt[q], p - r);
+    if (r) atomicAdd(&cnt[q + 1], r);
+    if (p > 1) loc[k] = atomicAdd(&nparts, p);
+  }
+  __syncthreads();
+  if (t < PP_CLASSES) {
+    if (cnt[t]) base[t] = atomicAdd(&cursor[t], cnt[t]);
+    cnt[t] = 0;
+  }
+  if (t == 0 && nparts) part0 = atomicAdd(&pcount[1], nparts);
+  __syncthreads();
+#pragma unroll
+  for (uint32_t k = 0; k < PP_PER; k++) {
+    const uint32_t b = (blockIdx.x * PP_PER + k) * PP_THREADS + t;
+    if (b >= total) continue;
+    const uint32_t bs = offsets[b], len = offsets[b + 1] - bs;
+    if (!len) continue;
+    uint32_t p, q, r;
+    pp_split(len, T, p, q, r);
+    const uint32_t s0 = base[q] + atomicAdd(&cnt[q], p - r);
+    const uint32_t s1 = r ? base[q + 1] + atomicAdd(&cnt[q + 1], r) : 0u;
+    const uint32_t pb = p > 1 ? part0 + loc[k] : 0u;
+    if (p > 1) pbase[b] = pb;
+    if (p > PP_COOP) {
+      const uint32_t e = atomicAdd(&nbig, 1u);
+      if (e < PP_BIG) {
+        bigb[e] = b;
+        bigs0[e] = s0;
+        bigs1[e] = s1;
+        bigpb[e] = pb;
+        continue;
+      }
+    }
+    for (uint32_t i = 0; i < p; i++) pp_write(b, bs, p, q, r, i, s0, s1, pb, pieces, partb);
+  }
+  __syncthreads();
+  const uint32_t nb = min(nbig, PP_BIG);
+  for (uint32_t e = 0; e < nb; e++) {
+    const uint32_t b = bigb[e], bs = offsets[b], len = offsets[b + 1] - bs;
+    uint32_t p, q, r;
+    pp_split(len, T, p, q, r);
+    for (uint32_t i = t; i < p; i += PP_THREADS) pp_write(b, bs, p, q, r, i, bigs0[e], bigs1[e], bigpb[e], pieces, partb);
+  }
+}
+
+int msm_piece_plan(gm_ctx* ctx, Arena& arena, MsmPlan& plan, uint32_t T) {
+  if (T == 0 || T > PIECE_MAX_LEN) {
+    set_error("msm piece plan: bad piece length");
+    return GM_ERR_INVALID;
+  }
+  hipStream_t st = ctx->stream;
+  const size_t M = plan.M, total = plan.total;
+  plan.T = T;
+  // one piece per T entries plus one per non-empty bucket; a cut bucket (len > T)
+  // has at most 2 len / T parts
+  plan.max_pieces = M / T + std::min(total, M) + 1;
+  plan.max_parts = std::min(2 * M / T, M / T + total) + 1;
+  if (plan.max_pieces >= (size_t(1) << 31)) {
+    set_error("msm piece plan: too many pieces");
+    return GM_ERR_INVALID;
+  }
+  int rc;
+  DevBuf pieces, pcount, pbase, partb, hist;
+  if ((rc = pieces.alloc(arena, sizeof(uint4) * plan.max_pieces)) || (rc = pcount.alloc(arena, 16)) ||
+      (rc = pbase.alloc(arena, sizeof(uint32_t) * total)) ||
+      (rc = partb.alloc(arena, sizeof(uint32_t) * plan.max_parts)) ||
+      (rc = hist.alloc(arena, sizeof(uint32_t) * 2 * PP_CLASSES)))
+    return rc;
+  uint32_t* h = hist.as<uint32_t>();
+  const unsigned blocks = blocks_for(total, PP_THREADS * PP_PER);
+  GM_HIP(hipMemsetAsync(h, 0, sizeof(uint32_t) * PP_CLASSES, st));
+  hipLaunchKernelGGL(k_msm_pp_hist, dim3(blocks), dim3(PP_THREADS), 0, st, plan.offsets, plan.total, T, h);
+  hipLaunchKernelGGL(k_msm_pp_scan, dim3(1), dim3(PP_THREADS), 0, st, h, h + PP_CLASSES, pcount.as<uint32_t>());
+  hipLaunchKernelGGL(k_msm_pp_scatter, dim3(blocks), dim3(PP_THREADS), 0, st, plan.offsets, plan.total, T,
+                     h + PP_CLASSES, pcount.as<uint32_t>(), pieces.as<uint4>(), pbase.as<uint32_t>(),
+                     partb.as<uint32_t>());
+  GM_HIP(hipGetLastError());
+  plan.pieces = pieces.as<uint4>();
+  plan.pcount = pcount.as<uint32_t>();
+  plan.pbase = pbase.as<uint32_t>();
+  plan.partb = partb.as<uint32_t>();
+  return GM_OK;
+}
+
 // Shared-bucket cost model: n*W accumulation adds + ~3 reduction adds per
 // bucket, paid once (not per window).  Picks c = 20 / W = 13 for 2^20 BN254
 // points and c = 22 / W = 12 for 2^24.

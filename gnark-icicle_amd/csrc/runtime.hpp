@@ -83,6 +83,7 @@ struct gm_ctx {
   std::map<int, void*> ntt_domains;
   int msm_c_override = 0;
   int msm_glv = -1;   // GLV split of plain MSMs: -1 = default (n <= 2^21), 0 off, 1 on
+  int msm_piece_len = 0;  // G1 piece length T (gm_set_msm_piece_len): 0 = the size rule
   // workspace arena (stack-discipline scopes), plus two more for MSMs whose host
   // tail is deferred (pipelined MSMs: gm_msm_async, the Groth16 MSM sequence)
   gm::ArenaState arena;

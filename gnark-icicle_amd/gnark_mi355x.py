@@ -41,7 +41,7 @@ FR_BYTES = 32
 SYMBOLS = [
     "gm_last_error", "gm_version", "gm_init", "gm_destroy", "gm_synchronize", "gm_trim",
     "gm_profile_enable", "gm_profile_reset", "gm_profile_get", "gm_profile_dump",
-    "gm_set_msm_window", "gm_set_msm_glv", "gm_malloc", "gm_free", "gm_copy_to_device", "gm_memcpy_h2d",
+    "gm_set_msm_window", "gm_set_msm_glv", "gm_set_msm_piece_len", "gm_malloc", "gm_free", "gm_copy_to_device", "gm_memcpy_h2d",
     "gm_memcpy_d2h", "gm_memcpy_d2d", "gm_copy_points_to_device", "gm_msm", "gm_msm_host_scalars", "gm_points_upload", "gm_msm_prepared", "gm_precompute_layout", "gm_points_upload_precomputed",
     "gm_msm_precomputed", "gm_kzg_commit", "gm_ntt",
     "gm_poly_ops", "gm_reverse_scalars", "gm_groth16_compute_h", "gm_g16_pk_upload", "gm_g16_pk_upload_ex", "gm_g16_pk_upload_shard",
@@ -108,6 +108,7 @@ def load_library(path: str = LIB_PATH):
     L.gm_profile_dump.argtypes = [vp, ctypes.c_char_p, sz]
     L.gm_set_msm_window.argtypes = [vp, i]
     L.gm_set_msm_glv.argtypes = [vp, i]
+    L.gm_set_msm_piece_len.argtypes = [vp, i]
     L.gm_malloc.argtypes = [vp, sz, pvp]
     L.gm_free.argtypes = [vp, vp]
     L.gm_copy_to_device.argtypes = [vp, vp, sz, pvp]
@@ -320,6 +321,10 @@ class Context:
     def set_msm_glv(self, mode: int):
         """GLV split of plain MSMs: 1 on, 0 off, -1 the size rule (on up to 2^21 points)."""
         _check(load_library().gm_set_msm_glv(self.handle, mode))
+
+    def set_msm_piece_len(self, t: int):
+        """G1 piece length (entries of one bucket per accumulation lane); 0 = the size rule."""
+        _check(load_library().gm_set_msm_piece_len(self.handle, t))
 
     # ---- MSM -----------------------------------------------------------------
     def msm(self, curve, scalars: DeviceBuffer, points: DeviceBuffer, n: int, g2: bool = False):

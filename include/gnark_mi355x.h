@@ -76,6 +76,10 @@ int gm_set_msm_window(gm_ctx* ctx, int c);
  * points unless GM_MSM_GLV=0; G2 also unless GM_MSM_GLV_G2=0).  Tuning / A-B
  * knob; results are identical either way. */
 int gm_set_msm_glv(gm_ctx* ctx, int mode);
+/* Test/tuning knob: G1 MSMs accumulate pieces of at most t entries of one
+ * bucket each (1..128; 0 = the built-in size rule).  Results are identical for
+ * every t. */
+int gm_set_msm_piece_len(gm_ctx* ctx, int t);
 
 /* ---- memory (iciclegnark CopyToDevice / CopyPointsToDevice /
  *      CopyG2PointsToDevice / FreeDevicePointer; icicle.go:44,47,65,90,95,
