@@ -43,7 +43,8 @@ SYMBOLS = [
     "gm_profile_enable", "gm_profile_reset", "gm_profile_get", "gm_profile_dump",
     "gm_set_msm_window", "gm_set_msm_glv", "gm_set_msm_piece_len", "gm_malloc", "gm_free", "gm_copy_to_device", "gm_memcpy_h2d",
     "gm_memcpy_d2h", "gm_memcpy_d2d", "gm_copy_points_to_device", "gm_msm", "gm_msm_host_scalars", "gm_points_upload", "gm_msm_prepared", "gm_precompute_layout", "gm_points_upload_precomputed",
-    "gm_msm_precomputed", "gm_kzg_commit", "gm_ntt",
+    "gm_msm_precomputed", "gm_kzg_commit", "gm_kzg_eval", "gm_poly_div_linear", "gm_poly_fold", "gm_kzg_open",
+    "gm_kzg_batch_open", "gm_ntt",
     "gm_poly_ops", "gm_reverse_scalars", "gm_groth16_compute_h", "gm_g16_pk_upload", "gm_g16_pk_upload_ex", "gm_g16_pk_upload_shard",
     "gm_g16_partial_bytes", "gm_g16_prove_partial", "gm_g16_finish",
     "gm_g16_pk_free", "gm_g16_pk_precomputed", "gm_g16_prove", "gm_g16_prove_device", "gm_jac_add", "gm_jac_to_affine",
@@ -124,6 +125,12 @@ def load_library(path: str = LIB_PATH):
     L.gm_points_upload_precomputed.argtypes = [vp, i, i, vp, sz, i, pvp]
     L.gm_msm_precomputed.argtypes = [vp, i, i, vp, vp, sz, i, sz, vp, vp]
     L.gm_kzg_commit.argtypes = [vp, i, vp, sz, vp, sz, vp]
+    psz = ctypes.POINTER(sz)
+    L.gm_kzg_eval.argtypes = [vp, i, pvp, psz, sz, vp, vp]
+    L.gm_poly_div_linear.argtypes = [vp, i, vp, sz, vp, vp, vp]
+    L.gm_poly_fold.argtypes = [vp, i, pvp, psz, sz, vp, vp]
+    L.gm_kzg_open.argtypes = [vp, i, vp, sz, vp, sz, vp, vp, vp]
+    L.gm_kzg_batch_open.argtypes = [vp, i, vp, sz, pvp, psz, sz, vp, vp, vp, vp]
     L.gm_ntt.argtypes = [vp, i, vp, sz, i, i, i]
     L.gm_poly_ops.argtypes = [vp, i, vp, vp, vp, sz, vp]
     L.gm_reverse_scalars.argtypes = [vp, i, vp, sz]
@@ -388,6 +395,63 @@ class Context:
         _check(load_library().gm_kzg_commit(self.handle, curve_id(curve), srs.ptr, srs.count, _p(c),
                                             c.size // FR_BYTES, _p(out)))
         return out.tobytes()
+
+    # ---- KZG openings on resident polynomials ----------------------------------
+    @staticmethod
+    def _poly_table(polys, lens):
+        """(pointer array, length array, k) of DeviceBuffer polynomials; lens
+        defaults to each buffer's size in elements, None is the empty polynomial."""
+        k = len(polys)
+        if lens is None:
+            lens = [0 if p is None else p.nbytes // FR_BYTES for p in polys]
+        ptrs = (ctypes.c_void_p * max(k, 1))(*[None if p is None else p.ptr for p in polys])
+        ls = (ctypes.c_size_t * max(k, 1))(*lens)
+        return ptrs, ls, k
+
+    def kzg_eval(self, curve, polys, z: bytes, lens=None) -> list:
+        """gm_kzg_eval: [f_i(z)] as 32-byte Montgomery elements."""
+        ptrs, ls, k = self._poly_table(polys, lens)
+        zz = _buf(z)
+        out = np.zeros(FR_BYTES * max(k, 1), np.uint8)
+        _check(load_library().gm_kzg_eval(self.handle, curve_id(curve), ptrs, ls, k, _p(zz), _p(out)))
+        b = out.tobytes()
+        return [b[FR_BYTES * j:FR_BYTES * (j + 1)] for j in range(k)]
+
+    def poly_div_linear(self, curve, f: DeviceBuffer, z: bytes, q: DeviceBuffer, m: int | None = None) -> bytes:
+        """gm_poly_div_linear: q <- (f - f(z)) / (X - z) (m - 1 elements); returns f(z)."""
+        m = f.nbytes // FR_BYTES if m is None else m
+        zz = _buf(z)
+        out = np.zeros(FR_BYTES, np.uint8)
+        _check(load_library().gm_poly_div_linear(self.handle, curve_id(curve), f.ptr, m, _p(zz),
+                                                 q.ptr if q is not None else None, _p(out)))
+        return out.tobytes()
+
+    def poly_fold(self, curve, polys, gamma: bytes, out: DeviceBuffer, lens=None):
+        """gm_poly_fold: out <- sum_i gamma^i f_i (max(lens) elements)."""
+        ptrs, ls, k = self._poly_table(polys, lens)
+        g = _buf(gamma)
+        _check(load_library().gm_poly_fold(self.handle, curve_id(curve), ptrs, ls, k, _p(g), out.ptr))
+
+    def kzg_open(self, curve, srs: DeviceBuffer, f: DeviceBuffer, z: bytes, m: int | None = None):
+        """kzg.Open on a resident polynomial: (claimed value, H affine) bytes."""
+        m = f.nbytes // FR_BYTES if m is None else m
+        zz = _buf(z)
+        val = np.zeros(FR_BYTES, np.uint8)
+        h = np.zeros(point_bytes(curve, False), np.uint8)
+        _check(load_library().gm_kzg_open(self.handle, curve_id(curve), srs.ptr, srs.count, f.ptr, m, _p(zz),
+                                          _p(val), _p(h)))
+        return val.tobytes(), h.tobytes()
+
+    def kzg_batch_open(self, curve, srs: DeviceBuffer, polys, z: bytes, gamma: bytes, lens=None):
+        """kzg.BatchOpenSinglePoint once gamma is known: (F(z), H affine) bytes for
+        F = sum_i gamma^i f_i."""
+        ptrs, ls, k = self._poly_table(polys, lens)
+        zz, g = _buf(z), _buf(gamma)
+        val = np.zeros(FR_BYTES, np.uint8)
+        h = np.zeros(point_bytes(curve, False), np.uint8)
+        _check(load_library().gm_kzg_batch_open(self.handle, curve_id(curve), srs.ptr, srs.count, ptrs, ls, k,
+                                                _p(zz), _p(g), _p(val), _p(h)))
+        return val.tobytes(), h.tobytes()
 
     def msm_on_device(self, scalars, points, n, curve="bn254"):
         """MsmOnDevice(scalars_d, points_d, count, convert=true) -> G1Jac bytes."""

@@ -164,6 +164,45 @@ int gm_msm_precomputed(gm_ctx* ctx, int curve, int g2, const void* scalars_dev, 
 int gm_kzg_commit(gm_ctx* ctx, int curve, const void* srs_prepared, size_t srs_len,
                   const void* coeffs_host, size_t n, void* digest_affine);
 
+/* ---- KZG openings (PLONK; prove.go:611 kzg.Open, :757 kzg.BatchOpenSinglePoint)
+ * The polynomial work of an opening on polynomials resident on the device
+ * (n Montgomery fr.Elements each, 16-byte aligned, e.g. from gm_copy_to_device):
+ * evaluation at z, the fold sum_i gamma^i f_i, and the division by X - z
+ * (gnark-crypto's dividePolyByXminusA).  Fr results are canonical, so values and
+ * quotient coefficients are gnark-crypto's bytes.  z, gamma and the returned
+ * values are single Montgomery fr.Elements in host memory.  polys_dev is a host
+ * array of k device pointers, lens their lengths in elements; k is not capped.
+ * GM_ERR_INVALID for k == 0 or m == 0.
+ *
+ * A batch opening takes two calls because the Fiat-Shamir gamma depends on the
+ * claimed values: upload the polynomials once, gm_kzg_eval, derive gamma on the
+ * host, gm_kzg_batch_open on the same buffers.
+ *
+ *  - gm_kzg_eval: values_host[i] = f_i(z), k elements (a length of 0 gives 0).
+ *  - gm_poly_div_linear: q_dev[0..m-2] = (f - f(z)) / (X - z), *value_host = f(z).
+ *    m >= 1; m == 1 writes nothing to q_dev.  q_dev must not overlap f_dev
+ *    (GM_ERR_INVALID if it does); f_dev is left unchanged.
+ *  - gm_poly_fold: out_dev[0..max(lens)-1] = sum_i gamma^i f_i; a polynomial
+ *    contributes nothing at and past its own length.
+ *  - gm_kzg_open: *claimed_host = f(z) and h_affine = the commitment of the
+ *    quotient over the first m - 1 points of a prepared SRS (gm_points_upload);
+ *    the quotient never leaves the device.  GM_ERR_INVALID if m > srs_len
+ *    (kzg.ErrInvalidPolynomialSize).  A constant polynomial (m == 1) gives the
+ *    identity (0, 0).
+ *  - gm_kzg_batch_open: the same for F = sum_i gamma^i f_i, m = max(lens);
+ *    *folded_value_host (may be NULL) = F(z) = sum_i gamma^i f_i(z). */
+int gm_kzg_eval(gm_ctx* ctx, int curve, const void* const* polys_dev, const size_t* lens, size_t k,
+                const void* z_host, void* values_host);
+int gm_poly_div_linear(gm_ctx* ctx, int curve, const void* f_dev, size_t m, const void* z_host,
+                       void* q_dev, void* value_host);
+int gm_poly_fold(gm_ctx* ctx, int curve, const void* const* polys_dev, const size_t* lens, size_t k,
+                 const void* gamma_host, void* out_dev);
+int gm_kzg_open(gm_ctx* ctx, int curve, const void* srs_prepared, size_t srs_len, const void* f_dev, size_t m,
+                const void* z_host, void* claimed_host, void* h_affine);
+int gm_kzg_batch_open(gm_ctx* ctx, int curve, const void* srs_prepared, size_t srs_len,
+                      const void* const* polys_dev, const size_t* lens, size_t k, const void* z_host,
+                      const void* gamma_host, void* folded_value_host, void* h_affine);
+
 /* ---- NTT (iciclegnark GenerateTwiddleFactors icicle.go:68,73;
  *      INttOnDevice :489,502; NttOnDevice :490; PolyOps :500;
  *      ReverseScalars :510; CPU twin fft.Domain.FFT/FFTInverse

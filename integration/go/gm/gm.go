@@ -457,6 +457,94 @@ func (s *SRS) Commit(coeffs unsafe.Pointer, n int, digest unsafe.Pointer) error 
 	return nil
 }
 
+// DevicePoly is a polynomial of n fr.Elements resident on device 0 (the input
+// of EvalPolys, SRS.Open and SRS.BatchOpen).  The empty polynomial holds no
+// device memory.
+type DevicePoly struct {
+	dev uintptr
+	n   int
+}
+
+// UploadPoly copies the n fr.Elements at coeffs to the device; coeffs is not
+// read when n is 0.
+func UploadPoly(coeffs unsafe.Pointer, n int) (*DevicePoly, error) {
+	ctx, err := Ctx()
+	if err != nil {
+		return nil, err
+	}
+	p := &DevicePoly{n: n}
+	if n == 0 {
+		return p, nil
+	}
+	var dev unsafe.Pointer
+	if rc := C.gm_copy_to_device(ctx, coeffs, C.size_t(32*n), &dev); rc != C.GM_OK {
+		return nil, lastErr("gm_copy_to_device", rc)
+	}
+	p.dev = uintptr(dev)
+	return p, nil
+}
+
+// Free releases the device copy (nil and empty polynomials are fine).
+func (p *DevicePoly) Free() {
+	if p != nil && p.dev != 0 {
+		C.gm_free(ctx0, unsafe.Pointer(p.dev))
+		p.dev = 0
+	}
+}
+
+// polyTable lays out the (address, length) arrays the C entries take.  The
+// addresses are device addresses held as integers: the arrays contain no Go
+// pointers, so they may be handed to C as they are.
+func polyTable(polys []*DevicePoly) ([]C.uintptr_t, []C.size_t) {
+	addrs := make([]C.uintptr_t, len(polys))
+	lens := make([]C.size_t, len(polys))
+	for i, p := range polys {
+		addrs[i] = C.uintptr_t(p.dev)
+		lens[i] = C.size_t(p.n)
+	}
+	return addrs, lens
+}
+
+// EvalPolys writes f_i(z) for every polynomial as fr.Elements at values
+// (len(polys) of them); z points at one fr.Element.
+func EvalPolys(curve int, polys []*DevicePoly, z, values unsafe.Pointer) error {
+	if len(polys) == 0 {
+		return nil
+	}
+	addrs, lens := polyTable(polys)
+	if rc := C.gm_kzg_eval(ctx0, C.int(curve), (*unsafe.Pointer)(unsafe.Pointer(&addrs[0])), &lens[0],
+		C.size_t(len(polys)), z, values); rc != C.GM_OK {
+		return lastErr("gm_kzg_eval", rc)
+	}
+	return nil
+}
+
+// Open is kzg.Open on a resident polynomial: the claimed value p(z) at claimed
+// (fr.Element) and the quotient's commitment at h (G1Affine).  The quotient
+// stays on the device.
+func (s *SRS) Open(p *DevicePoly, z, claimed, h unsafe.Pointer) error {
+	if rc := C.gm_kzg_open(ctx0, s.curve, s.dev, C.size_t(s.n), unsafe.Pointer(p.dev), C.size_t(p.n), z, claimed,
+		h); rc != C.GM_OK {
+		return lastErr("gm_kzg_open", rc)
+	}
+	return nil
+}
+
+// BatchOpen is the second half of kzg.BatchOpenSinglePoint, once gamma is known
+// from the claimed values (EvalPolys): the commitment at h of the quotient of
+// F = sum_i gamma^i polys[i] by X - z, and F(z) at folded (may be nil).
+func (s *SRS) BatchOpen(polys []*DevicePoly, z, gamma, folded, h unsafe.Pointer) error {
+	if len(polys) == 0 {
+		return errors.New("gnark_mi355x: batch opening of no polynomials")
+	}
+	addrs, lens := polyTable(polys)
+	if rc := C.gm_kzg_batch_open(ctx0, s.curve, s.dev, C.size_t(s.n), (*unsafe.Pointer)(unsafe.Pointer(&addrs[0])),
+		&lens[0], C.size_t(len(polys)), z, gamma, folded, h); rc != C.GM_OK {
+		return lastErr("gm_kzg_batch_open", rc)
+	}
+	return nil
+}
+
 // NTT runs an in-place fft.Domain FFT / FFTInverse of n fr.Elements at data
 // (host memory; copied to and from device 0).
 func NTT(curve int, data unsafe.Pointer, n int, inverse, dit, coset bool) error {

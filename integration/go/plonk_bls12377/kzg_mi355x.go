@@ -10,12 +10,15 @@
 //     commitLagrange; kzg.Commit(p, pk.Kzg) at :718 and the three quotient
 //     commitments of commitToQuotient (:1154-1170) -> commitCanonical; the
 //     opening quotients of kzg.Open (:611) and kzg.BatchOpenSinglePoint (:757)
-//     -> open / batchOpen: the quotient polynomial is formed on the host exactly
-//     as gnark-crypto's kzg does (Horner evaluation, synthetic division by
-//     X - z), and only its commitment -- the MSM -- runs on the GPU (gm_kzg_commit
-//     over the SRS kept resident, same digest bytes as kzg.Commit,
-//     tests/test_msm_gpu.py::test_kzg_commit_and_prepared_msm).  The SRS is
-//     selected explicitly by the caller, never by pointer identity.
+//     -> open / batchOpen: the polynomials are uploaded once; the claimed
+//     values, the fold sum_i gamma^i f_i and the division by X - z run on the
+//     device (gm_kzg_eval, gm_kzg_open, gm_kzg_batch_open: the same canonical Fr
+//     bytes as gnark-crypto's Horner evaluation and dividePolyByXminusA,
+//     tests/test_kzg_open_gpu.py), and the quotient goes from device memory
+//     straight into the MSM over the SRS kept resident (same digest bytes as
+//     kzg.Commit, tests/test_msm_gpu.py::test_kzg_commit_and_prepared_msm).
+//     Only gamma is derived on the host, between the two device steps.  The SRS
+//     is selected explicitly by the caller, never by pointer identity.
 //  2. Every n- and 4n-size FFT.  The domain0 ToCanonical / ToLagrange of
 //     computeNumerator (:949, :967, :1016) and of computeLinearizedPolynomial
 //     (:1301) -> toCanonical / toLagrange, and divideByZH's domain1 coset
@@ -124,41 +127,25 @@ func (d *kzgDevice) commitCanonical(p []fr.Element) (kzg.Digest, error) {
 	return commitWith(d.canonical, d.nCanon, p)
 }
 
-// evalAt is p(z) by Horner (gnark-crypto kzg's eval).
-func evalAt(p []fr.Element, z fr.Element) fr.Element {
-	var r fr.Element
-	for i := len(p) - 1; i >= 0; i-- {
-		r.Mul(&r, &z).Add(&r, &p[i])
-	}
-	return r
-}
-
-// quotientByXminusZ returns (f(X) - fz) / (X - z), computed in place in f
-// (synthetic division; the result is f[1:], of degree deg f - 1).  The
-// quotient is unique, so its commitment is kzg.Open's H byte for byte.
-func quotientByXminusZ(f []fr.Element, fz, z fr.Element) []fr.Element {
-	f[0].Sub(&f[0], &fz)
-	var t fr.Element
-	for i := len(f) - 2; i >= 0; i-- {
-		t.Mul(&f[i+1], &z)
-		f[i].Add(&f[i], &t)
-	}
-	return f[1:]
-}
-
-// open replaces kzg.Open(p, z, pk.Kzg) (prove.go:611).
+// open replaces kzg.Open(p, z, pk.Kzg) (prove.go:611): p is uploaded once, the
+// claimed value p(z) and the quotient (p - p(z)) / (X - z) are formed on the
+// device (gm_kzg_open) and the quotient goes straight into the MSM.  The
+// quotient is unique and Fr results are canonical, so H is kzg.Open's byte for
+// byte.
 func (d *kzgDevice) open(p []fr.Element, z fr.Element) (kzg.OpeningProof, error) {
 	if len(p) == 0 || len(p) > d.nCanon {
 		return kzg.OpeningProof{}, kzg.ErrInvalidPolynomialSize
 	}
-	res := kzg.OpeningProof{ClaimedValue: evalAt(p, z)}
-	q := make([]fr.Element, len(p))
-	copy(q, p)
-	h, err := d.commitCanonical(quotientByXminusZ(q, res.ClaimedValue, z))
+	dp, err := gm.UploadPoly(unsafe.Pointer(&p[0]), len(p))
 	if err != nil {
 		return kzg.OpeningProof{}, err
 	}
-	res.H.Set(&h)
+	defer dp.Free()
+	var res kzg.OpeningProof
+	if err := d.canonical.Open(dp, unsafe.Pointer(&z), unsafe.Pointer(&res.ClaimedValue),
+		unsafe.Pointer(&res.H)); err != nil {
+		return kzg.OpeningProof{}, err
+	}
 	return res, nil
 }
 
@@ -198,9 +185,11 @@ func deriveGamma(z fr.Element, digests []kzg.Digest, claimed []fr.Element, hf ha
 var errBatchCheck = errors.New("gnark_mi355x: GPU batch opening failed its verification")
 
 // batchOpen replaces kzg.BatchOpenSinglePoint(polys, digests, z, hf, pk.Kzg,
-// data...) (prove.go:757): claimed values f_i(z), gamma, the folded polynomial
-// F = sum_i gamma^i f_i and its quotient (F - F(z)) / (X - z) on the host, the
-// commitment on the GPU.  The result is checked with kzg.BatchVerifySinglePoint
+// data...) (prove.go:757).  The polynomials are uploaded once and stay on the
+// device for both steps: the claimed values f_i(z) (gm_kzg_eval), then -- gamma
+// depends on them, so it is derived on the host in between -- the fold
+// F = sum_i gamma^i f_i, its quotient (F - F(z)) / (X - z) and the commitment
+// (gm_kzg_batch_open).  The result is checked with kzg.BatchVerifySinglePoint
 // (gnark-crypto's own transcript); errBatchCheck tells the caller to use the
 // CPU opening instead.
 func (d *kzgDevice) batchOpen(polys [][]fr.Element, digests []kzg.Digest, z fr.Element, hf hash.Hash,
@@ -208,40 +197,46 @@ func (d *kzgDevice) batchOpen(polys [][]fr.Element, digests []kzg.Digest, z fr.E
 	if len(polys) != len(digests) || len(polys) == 0 {
 		return kzg.BatchOpeningProof{}, kzg.ErrInvalidNbDigests
 	}
-	var res kzg.BatchOpeningProof
-	res.ClaimedValues = make([]fr.Element, len(polys))
 	largest := 0
 	for i := range polys {
 		if len(polys[i]) > d.nCanon {
 			return kzg.BatchOpeningProof{}, kzg.ErrInvalidPolynomialSize
 		}
-		res.ClaimedValues[i] = evalAt(polys[i], z)
 		if len(polys[i]) > largest {
 			largest = len(polys[i])
 		}
+	}
+	if largest == 0 {
+		return kzg.BatchOpeningProof{}, errBatchCheck
+	}
+	devs := make([]*gm.DevicePoly, len(polys))
+	defer func() {
+		for _, dp := range devs {
+			dp.Free()
+		}
+	}()
+	var err error
+	for i := range polys {
+		var src unsafe.Pointer
+		if len(polys[i]) > 0 {
+			src = unsafe.Pointer(&polys[i][0])
+		}
+		if devs[i], err = gm.UploadPoly(src, len(polys[i])); err != nil {
+			return kzg.BatchOpeningProof{}, err
+		}
+	}
+	var res kzg.BatchOpeningProof
+	res.ClaimedValues = make([]fr.Element, len(polys))
+	if err = gm.EvalPolys(gm.BLS12_377, devs, unsafe.Pointer(&z), unsafe.Pointer(&res.ClaimedValues[0])); err != nil {
+		return kzg.BatchOpeningProof{}, err
 	}
 	hf.Reset()
 	gamma, err := deriveGamma(z, digests, res.ClaimedValues, hf, data...)
 	if err != nil {
 		return kzg.BatchOpeningProof{}, err
 	}
-	// F(z) = sum_i gamma^i f_i(z) and F = sum_i gamma^i f_i
-	folded := res.ClaimedValues[len(polys)-1]
-	for i := len(polys) - 2; i >= 0; i-- {
-		folded.Mul(&folded, &gamma).Add(&folded, &res.ClaimedValues[i])
-	}
-	f := make([]fr.Element, largest)
-	copy(f, polys[0])
-	var gi, t fr.Element
-	gi.SetOne()
-	for i := 1; i < len(polys); i++ {
-		gi.Mul(&gi, &gamma)
-		for j := range polys[i] {
-			t.Mul(&polys[i][j], &gi)
-			f[j].Add(&f[j], &t)
-		}
-	}
-	if res.H, err = d.commitCanonical(quotientByXminusZ(f, folded, z)); err != nil {
+	if err = d.canonical.BatchOpen(devs, unsafe.Pointer(&z), unsafe.Pointer(&gamma), nil,
+		unsafe.Pointer(&res.H)); err != nil {
 		return kzg.BatchOpeningProof{}, err
 	}
 	hf.Reset()
