@@ -11,6 +11,7 @@
 #include "curves.hpp"
 #include "groth16.hpp"
 #include "kzg.hpp"
+#include "plonk.hpp"
 #include "msm.hpp"
 #include "ntt.hpp"
 #include "runtime.hpp"
@@ -851,6 +852,24 @@ int gm_kzg_batch_open(gm_ctx* ctx, int curve, const void* srs, size_t srs_len, c
   uint64_t value[4];
   if (!rc) rc = kzg_open_resident(ctx, curve, srs, srs_len, folded.p, m, z_host, value, h_affine);
   if (!rc && folded_value_host) memcpy(folded_value_host, value, sizeof(value));
+  return rc;
+}
+
+// ---- PLONK quotient on resident polynomials (plonk.hip) -----------------------------
+int gm_plonk_quotient(gm_ctx* ctx, int curve, const gm_plonk_quotient_in* in, void* h_dev) {
+  if (!ctx || !in || !h_dev) return GM_ERR_INVALID;
+  if (int rc = check_curve(curve)) return rc;
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  int rc;
+  {
+    ProfScope ps(ctx, "plonk_quotient_call");
+    rc = curve == GM_BN254 ? plonk_quotient_device<CurveBN254>(ctx, in, h_dev)
+                           : plonk_quotient_device<CurveBLS12377>(ctx, in, h_dev);
+  }
+  // also after a refusal part-way: nothing queued may outlive the call's workspace
+  GM_HIP(hipStreamSynchronize(ctx->stream));
+  prof_collect(ctx);
   return rc;
 }
 

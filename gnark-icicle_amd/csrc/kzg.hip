@@ -249,19 +249,6 @@ __global__ void __launch_bounds__(256) k_poly_fold(const PolyRef* __restrict__ p
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-// gnark-form host element -> internal form in gnark's word layout: x 2^(29 N) =
-// (x 2^(32 NG)) 2^(29 N - 32 NG), a product with a small power of two
-template <class C>
-static FeG<typename C::Fr> to_internal_words(const host::F<typename C::HFr>& x) {
-  using Fr = typename C::Fr;
-  static const host::F<typename C::HFr> kin = host::from_u64<typename C::HFr>(1ull << (RADIX * Fr::N - 32 * Fr::NG));
-  const host::F<typename C::HFr> y = x * kin;
-  FeG<Fr> r;
-  static_assert(sizeof(r.w) == sizeof(y.v), "gnark layout");
-  memcpy(r.w, y.v, sizeof(r.w));
-  return r;
-}
-
 template <class C>
 static PolyPoint<typename C::Fr> make_point(const void* z_host) {
   host::F<typename C::HFr> p;

@@ -775,7 +775,12 @@ struct NttPass {
 };
 
 // full-size element-wise tables (built on first use, n internal-form elements)
-enum NttTab { TAB_G_NAT, TAB_G_BREV, TAB_GI_NAT, TAB_GI_BREV, TAB_H_POST, TAB_COUNT };
+enum NttTab {
+  TAB_G_NAT, TAB_G_BREV, TAB_GI_NAT, TAB_GI_BREV, TAB_H_POST,
+  TAB_Q1_NAT, TAB_Q2_NAT, TAB_Q3_NAT,  // PLONK quotient: powers of the coset shifts g w_4n^i
+  TAB_W_BREV,                          // w^brev(i): the domain's points in DIF output order
+  TAB_COUNT
+};
 
 template <class C>
 struct NttDomain {
@@ -903,6 +908,8 @@ static int domain_build(gm_ctx* ctx, int logn, NttDomain<C>** out) {
 //   G_NAT[i] = g^i, G_BREV[i] = g^brev(i)                    (forward coset, on load)
 //   GI_NAT[i] = g^-i / n, GI_BREV[i] = g^-brev(i) / n        (inverse coset, on store)
 //   H_POST[i] = g^-brev(i) / (n (g^n - 1))                   (computeH final INTT)
+//   Qk_NAT[i] = (g w_4n^k)^i, k = 1..3                       (coset4_ntt_device, on load)
+//   W_BREV[i] = w^brev(i)                                    (ntt_brev_roots)
 template <class C>
 static int domain_table(gm_ctx* ctx, NttDomain<C>* d, int which, const Fe<typename C::Fr>** out) {
   using Fr = typename C::Fr;
@@ -919,8 +926,13 @@ static int domain_table(gm_ctx* ctx, NttDomain<C>* d, int which, const Fe<typena
       uint64_t e[1] = {d->n};
       base = gi;
       mult = d->ninv * host::finv(host::fpow(d->g, e, 1) - HF::one());
+    } else if (which >= TAB_Q1_NAT && which <= TAB_Q3_NAT) {
+      uint64_t e[1] = {(uint64_t)(which - TAB_Q1_NAT + 1)};
+      base = d->g * host::fpow(host_omega<C>(d->logn + 2), e, 1);
+    } else if (which == TAB_W_BREV) {
+      base = d->omega;
     }
-    const bool brev = which == TAB_G_BREV || which == TAB_GI_BREV || which == TAB_H_POST;
+    const bool brev = which == TAB_G_BREV || which == TAB_GI_BREV || which == TAB_H_POST || which == TAB_W_BREV;
     auto k = brev ? k_gen_coset<Fr, true> : k_gen_coset<Fr, false>;
     hipLaunchKernelGGL(k, dim3(blocks_for(d->n, 256)), dim3(256), 0, ctx->stream, (Fe<Fr>*)d->tab[which], d->n,
                        d->logn, to_dev<HF, Fr>(base), to_dev<HF, Fr>(mult));
@@ -1183,6 +1195,61 @@ int compute_h_finish(gm_ctx* ctx, void* a, const void* b, const void* c, size_t 
   return transform<C>(ctx, d, a, true, false, false, fz);
 }
 
+// ---------------------------------------------------------------------------
+// PLONK quotient building blocks (plonk.hip): the 4n domain <w1> is the union of
+// the four cosets w1^i <w0> of the n domain, w0 = w1^4.
+// ---------------------------------------------------------------------------
+template <class C>
+static bool coset4_size_ok(size_t n) {
+  const int logn = log2_exact(n);
+  return logn >= 1 && logn + 2 <= C::TWO_ADICITY && logn + 2 <= 30;
+}
+
+template <class C>
+int coset4_shift(size_t n, int i, void* shift_host) {
+  if (!coset4_size_ok<C>(n) || i < 0 || i > 3) {
+    set_error("coset4: n must be a power of two with 4n within the 2-adicity, i in 0..3");
+    return GM_ERR_INVALID;
+  }
+  using HFr = typename C::HFr;
+  uint64_t e[1] = {(uint64_t)i};
+  const host::F<HFr> c = host::from_u64<HFr>(C::COSET_GEN) * host::fpow(host_omega<C>(log2_exact(n) + 2), e, 1);
+  memcpy(shift_host, c.v, sizeof(c.v));
+  return GM_OK;
+}
+
+// Forward DIF with (g w1^i)^j multiplied in on load: natural coefficients in,
+// position p holds the value at g w1^i w0^brev(p).
+template <class C>
+int coset4_ntt_device(gm_ctx* ctx, void* v, size_t n, int i) {
+  using Fr = typename C::Fr;
+  if (!coset4_size_ok<C>(n) || i < 0 || i > 3) {
+    set_error("coset4: n must be a power of two with 4n within the 2-adicity, i in 0..3");
+    return GM_ERR_INVALID;
+  }
+  NttDomain<C>* d;
+  int rc;
+  if ((rc = get_domain<C>(ctx, log2_exact(n), &d))) return rc;
+  NttFuse<Fr> fz;
+  if ((rc = domain_table<C>(ctx, d, i == 0 ? TAB_G_NAT : TAB_Q1_NAT + (i - 1), &fz.pre))) return rc;
+  return transform<C>(ctx, d, v, false, false, false, fz);
+}
+
+template <class C>
+int ntt_brev_roots(gm_ctx* ctx, size_t n, const void** tab) {
+  const int logn = log2_exact(n);
+  if (logn < 0 || logn > C::TWO_ADICITY || logn > 30) {
+    set_error("ntt: n must be a power of two within the 2-adicity");
+    return GM_ERR_INVALID;
+  }
+  NttDomain<C>* d;
+  const Fe<typename C::Fr>* t;
+  int rc;
+  if ((rc = get_domain<C>(ctx, logn, &d)) || (rc = domain_table<C>(ctx, d, TAB_W_BREV, &t))) return rc;
+  *tab = t;
+  return GM_OK;
+}
+
 #define GM_NTT_INST(C)                                                                   \
   template int ntt_device<C>(gm_ctx*, void*, size_t, bool, bool, bool);                   \
   template int poly_ops_device<C>(gm_ctx*, void*, const void*, const void*, size_t,        \
@@ -1194,7 +1261,10 @@ int compute_h_finish(gm_ctx* ctx, void* a, const void* b, const void* c, size_t 
   template int bitrev_copy_device<C>(gm_ctx*, void*, const void*, size_t);                 \
   template int poly_ops_vec_device<C>(gm_ctx*, void*, const void*, const void*, const void*, size_t); \
   template int ntt_domain_prepare<C>(gm_ctx*, size_t);                                           \
-  template int compute_h_prepare<C>(gm_ctx*, size_t);
+  template int compute_h_prepare<C>(gm_ctx*, size_t);                                           \
+  template int coset4_shift<C>(size_t, int, void*);                                              \
+  template int coset4_ntt_device<C>(gm_ctx*, void*, size_t, int);                                \
+  template int ntt_brev_roots<C>(gm_ctx*, size_t, const void**);
 GM_NTT_INST(CurveBN254)
 GM_NTT_INST(CurveBLS12377)
 

@@ -31,5 +31,17 @@ int ntt_domain_prepare(gm_ctx* ctx, size_t n);
 // the domain and computeH's tables for n, ahead of the first prove (key upload)
 template <class C>
 int compute_h_prepare(gm_ctx* ctx, size_t n);
+// PLONK quotient building blocks (plonk.hip).  With w1 the generator of the 4n
+// domain and w0 = w1^4, the 4n coset g <w1> is the union of g w1^i <w0>, i < 4.
+// *shift_host = g w1^i (one gnark element)
+template <class C>
+int coset4_shift(size_t n, int i, void* shift_host);
+// v: n coefficients, natural order -> in place, position p holds the value at
+// g w1^i w0^brev(p) (forward DIF, the shift's powers multiplied in on load)
+template <class C>
+int coset4_ntt_device(gm_ctx* ctx, void* v, size_t n, int i);
+// *tab: n internal-form elements w0^brev(p), cached with the domain
+template <class C>
+int ntt_brev_roots(gm_ctx* ctx, size_t n, const void** tab);
 void ntt_domains_free(gm_ctx* ctx);
 }  // namespace gm

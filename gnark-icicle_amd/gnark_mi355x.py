@@ -44,7 +44,7 @@ SYMBOLS = [
     "gm_set_msm_window", "gm_set_msm_glv", "gm_set_msm_piece_len", "gm_malloc", "gm_free", "gm_copy_to_device", "gm_memcpy_h2d",
     "gm_memcpy_d2h", "gm_memcpy_d2d", "gm_copy_points_to_device", "gm_msm", "gm_msm_host_scalars", "gm_points_upload", "gm_msm_prepared", "gm_precompute_layout", "gm_points_upload_precomputed",
     "gm_msm_precomputed", "gm_kzg_commit", "gm_kzg_eval", "gm_poly_div_linear", "gm_poly_fold", "gm_kzg_open",
-    "gm_kzg_batch_open", "gm_ntt",
+    "gm_kzg_batch_open", "gm_plonk_quotient", "gm_ntt",
     "gm_poly_ops", "gm_reverse_scalars", "gm_groth16_compute_h", "gm_g16_pk_upload", "gm_g16_pk_upload_ex", "gm_g16_pk_upload_shard",
     "gm_g16_partial_bytes", "gm_g16_prove_partial", "gm_g16_finish",
     "gm_g16_pk_free", "gm_g16_pk_precomputed", "gm_g16_prove", "gm_g16_prove_device", "gm_jac_add", "gm_jac_to_affine",
@@ -63,6 +63,17 @@ TESTHOOKS_PATH = os.path.join(os.path.dirname(LIB_PATH), "libgnark_mi355x_testho
 
 class GmError(RuntimeError):
     pass
+
+
+PLONK_POLYS = ("ql", "qr", "qm", "qo", "qk", "s1", "s2", "s3", "l", "r", "o", "z")
+
+
+class _PlonkQuotientIn(ctypes.Structure):
+    """gm_plonk_quotient_in (include/gnark_mi355x.h)."""
+    _fields_ = ([("n", ctypes.c_size_t)] + [(k, ctypes.c_void_p) for k in PLONK_POLYS]
+                + [("nb_bsb", ctypes.c_size_t), ("qcp", ctypes.POINTER(ctypes.c_void_p)),
+                   ("pi2", ctypes.POINTER(ctypes.c_void_p))]
+                + [(k, ctypes.c_void_p) for k in ("bl", "br", "bo", "bz", "alpha", "beta", "gamma")])
 
 
 _lib = None
@@ -131,6 +142,7 @@ def load_library(path: str = LIB_PATH):
     L.gm_poly_fold.argtypes = [vp, i, pvp, psz, sz, vp, vp]
     L.gm_kzg_open.argtypes = [vp, i, vp, sz, vp, sz, vp, vp, vp]
     L.gm_kzg_batch_open.argtypes = [vp, i, vp, sz, pvp, psz, sz, vp, vp, vp, vp]
+    L.gm_plonk_quotient.argtypes = [vp, i, ctypes.POINTER(_PlonkQuotientIn), vp]
     L.gm_ntt.argtypes = [vp, i, vp, sz, i, i, i]
     L.gm_poly_ops.argtypes = [vp, i, vp, vp, vp, sz, vp]
     L.gm_reverse_scalars.argtypes = [vp, i, vp, sz]
@@ -452,6 +464,30 @@ class Context:
         _check(load_library().gm_kzg_batch_open(self.handle, curve_id(curve), srs.ptr, srs.count, ptrs, ls, k,
                                                 _p(zz), _p(g), _p(val), _p(h)))
         return val.tobytes(), h.tobytes()
+
+    # ---- PLONK quotient on resident polynomials ---------------------------------
+    def plonk_quotient(self, curve, n: int, polys: dict, qcp, pi2, blinds: dict, alpha: bytes, beta: bytes,
+                       gamma: bytes, h: DeviceBuffer):
+        """gm_plonk_quotient: h <- the quotient (4n elements, canonical, regular).
+        polys: DeviceBuffers keyed by PLONK_POLYS (n unblinded elements each); qcp /
+        pi2: lists of DeviceBuffers (BSB22 gates, may be empty; None passes a NULL
+        table); blinds: bytes keyed bl, br, bo (2 elements) and bz (3 elements)."""
+        a = _PlonkQuotientIn()
+        a.n = n
+        for k in PLONK_POLYS:
+            setattr(a, k, polys[k].ptr)
+        nb = max(len(qcp) if qcp is not None else 0, len(pi2) if pi2 is not None else 0)
+        a.nb_bsb = nb
+        tabs = []
+        for name, t in (("qcp", qcp), ("pi2", pi2)):
+            if t is not None and nb:
+                arr = (ctypes.c_void_p * nb)(*[b.ptr for b in t])
+                tabs.append(arr)
+                setattr(a, name, ctypes.cast(arr, ctypes.POINTER(ctypes.c_void_p)))
+        keep = [_buf(blinds[k]) for k in ("bl", "br", "bo", "bz")] + [_buf(alpha), _buf(beta), _buf(gamma)]
+        for k, v in zip(("bl", "br", "bo", "bz", "alpha", "beta", "gamma"), keep):
+            setattr(a, k, v.ctypes.data)
+        _check(load_library().gm_plonk_quotient(self.handle, curve_id(curve), ctypes.byref(a), h.ptr))
 
     def msm_on_device(self, scalars, points, n, curve="bn254"):
         """MsmOnDevice(scalars_d, points_d, count, convert=true) -> G1Jac bytes."""

@@ -203,6 +203,50 @@ int gm_kzg_batch_open(gm_ctx* ctx, int curve, const void* srs_prepared, size_t s
                       const void* const* polys_dev, const size_t* lens, size_t k, const void* z_host,
                       const void* gamma_host, void* folded_value_host, void* h_affine);
 
+/* ---- PLONK quotient (backend/plonk/bls12-377/prove.go:771-1034 computeNumerator,
+ *      :1178-1231 divideByZH) ----------------------------------------------------
+ * The quotient stage on polynomials resident on the device: h_dev receives h, the
+ * inputs stay where they are and are left unchanged.
+ *
+ * Every device polynomial is n Montgomery fr.Elements in the canonical basis,
+ * regular (natural) layout, 16-byte aligned.  l, r, o, z are NOT blinded: the
+ * blinding polynomials come as host coefficients (bl, br, bo: 2 elements, degree
+ * 1; bz: 3 elements, degree 2).  qcp / pi2 are host arrays of nb_bsb device
+ * pointers (the BSB22 commitment gates; nb_bsb may be 0, the tables then are not
+ * read).  alpha, beta, gamma are single host elements.  h_dev holds 4n elements
+ * and must overlap no input.
+ *
+ * With g = FrMultiplicativeGen, w1 the generator of the 4n domain, w0 = w1^4,
+ * Z_H = X^n - 1, L~ = L + Z_H bl (R~, O~, Z~ likewise), L1 = Z_H / (n (X - 1)):
+ *   T = Ql L~ + Qr R~ + Qm L~ R~ + Qo O~ + Qk + sum_i Qcp_i PI2_i
+ *     + alpha [ (L~ + beta S1 + gamma)(R~ + beta S2 + gamma)(O~ + beta S3 + gamma) Z~(w0 X)
+ *             - (L~ + beta X + gamma)(R~ + beta g X + gamma)(O~ + beta g^2 X + gamma) Z~ ]
+ *     + alpha^2 (Z~ - 1) L1
+ * and h is the polynomial of degree < 4n with h(x) = T(x) / Z_H(x) at the 4n
+ * points x = g w1^k: for a satisfying witness the quotient (degree <= 3n + 5),
+ * for any other input still well defined.  h_dev is in canonical, regular order;
+ * the prover's h1, h2, h3 are h[0:n+2], h[n+2:2n+4], h[2n+4:3n+6] and can go into
+ * gm_msm_prepared where they lie.  Every element is fully reduced, so the bytes
+ * are gnark's.  StatisticalZK's randomised h coefficients are the caller's.
+ *
+ * GM_ERR_INVALID: NULL context (checked before any device call), NULL struct or
+ * required pointer, n not a power of two or n < 8 (the reference's 8n domain for
+ * tiny circuits is not built), nb_bsb > 0 with a NULL table or entry, a
+ * misaligned pointer, h_dev overlapping an input.  Scratch ((13 + 2 nb_bsb) n
+ * elements) comes from the context's workspace; gm_trim releases it. */
+typedef struct {
+  size_t n;                        /* domain0 size: a power of two, >= 8 */
+  const void *ql, *qr, *qm, *qo, *qk, *s1, *s2, *s3;  /* device, n Fr each */
+  const void *l, *r, *o, *z;       /* device, n Fr each, NOT blinded */
+  size_t nb_bsb;                   /* BSB22 gates, may be 0 */
+  const void* const* qcp;          /* host array of nb_bsb device pointers */
+  const void* const* pi2;          /* host array of nb_bsb device pointers */
+  const void *bl, *br, *bo;        /* host, 2 Fr each (blinding, degree 1) */
+  const void *bz;                  /* host, 3 Fr (degree 2) */
+  const void *alpha, *beta, *gamma;/* host, 1 Fr each */
+} gm_plonk_quotient_in;
+int gm_plonk_quotient(gm_ctx* ctx, int curve, const gm_plonk_quotient_in* in, void* h_dev);
+
 /* ---- NTT (iciclegnark GenerateTwiddleFactors icicle.go:68,73;
  *      INttOnDevice :489,502; NttOnDevice :490; PolyOps :500;
  *      ReverseScalars :510; CPU twin fft.Domain.FFT/FFTInverse

@@ -545,6 +545,115 @@ func (s *SRS) BatchOpen(polys []*DevicePoly, z, gamma, folded, h unsafe.Pointer)
 	return nil
 }
 
+// AllocPoly reserves room for n fr.Elements on the device (the output of
+// PlonkQuotient); nothing is uploaded.
+func AllocPoly(n int) (*DevicePoly, error) {
+	ctx, err := Ctx()
+	if err != nil {
+		return nil, err
+	}
+	var dev unsafe.Pointer
+	if rc := C.gm_malloc(ctx, C.size_t(32*n), &dev); rc != C.GM_OK {
+		return nil, lastErr("gm_malloc", rc)
+	}
+	return &DevicePoly{dev: uintptr(dev), n: n}, nil
+}
+
+// Download copies n fr.Elements starting at element off back to dst.
+func (p *DevicePoly) Download(dst unsafe.Pointer, off, n int) error {
+	if off < 0 || n < 0 || off+n > p.n {
+		return errors.New("gnark_mi355x: download outside the polynomial")
+	}
+	if n == 0 {
+		return nil
+	}
+	if rc := C.gm_memcpy_d2h(ctx0, dst, devAt(p, off), C.size_t(32*n)); rc != C.GM_OK {
+		return lastErr("gm_memcpy_d2h", rc)
+	}
+	return nil
+}
+
+// CommitResident is kzg.Commit of the n coefficients of p starting at element
+// off, read where they lie on the device (the h1, h2, h3 of PlonkQuotient).
+func (s *SRS) CommitResident(p *DevicePoly, off, n int, digest unsafe.Pointer) error {
+	if off < 0 || n <= 0 || off+n > p.n || n > s.n {
+		return errors.New("gnark_mi355x: resident commit outside the polynomial or the SRS")
+	}
+	if rc := C.gm_msm_prepared(ctx0, s.curve, 0, devAt(p, off), s.dev, C.size_t(n), nil, digest); rc != C.GM_OK {
+		return lastErr("gm_msm_prepared", rc)
+	}
+	return nil
+}
+
+// devAt is the device address of element off of p: a device address, never a Go
+// pointer.
+func devAt(p *DevicePoly, off int) unsafe.Pointer {
+	return unsafe.Pointer(p.dev + uintptr(32*off))
+}
+
+// QuotientInput mirrors gm_plonk_quotient_in.  The polynomials are n canonical,
+// regular, unblinded fr.Elements each, resident on the device; Bl, Br, Bo (2
+// fr.Elements), Bz (3) and Alpha, Beta, Gamma (1) point at host memory.
+type QuotientInput struct {
+	N                              int
+	Ql, Qr, Qm, Qo, Qk, S1, S2, S3 *DevicePoly
+	L, R, O, Z                     *DevicePoly
+	Qcp, Pi2                       []*DevicePoly
+	Bl, Br, Bo, Bz                 unsafe.Pointer
+	Alpha, Beta, Gamma             unsafe.Pointer
+}
+
+// PlonkQuotient leaves the quotient h (4 q.N fr.Elements, canonical, regular) in
+// h: computeNumerator + divideByZH (prove.go:771-1034, :1178-1231) on resident
+// polynomials.  cgo rule as for cHost: &in is a Go pointer handed to C, so the
+// host pointers stored in it and the two address tables are pinned for the call;
+// the tables themselves hold device addresses as integers, no Go pointers.
+func PlonkQuotient(curve int, q *QuotientInput, h *DevicePoly) error {
+	if len(q.Qcp) != len(q.Pi2) {
+		return errors.New("gnark_mi355x: qcp and pi2 differ in length")
+	}
+	if h == nil || h.n < 4*q.N {
+		return errors.New("gnark_mi355x: the quotient needs 4n elements")
+	}
+	for _, p := range []*DevicePoly{q.Ql, q.Qr, q.Qm, q.Qo, q.Qk, q.S1, q.S2, q.S3, q.L, q.R, q.O, q.Z} {
+		if p == nil || p.n != q.N {
+			return errors.New("gnark_mi355x: every quotient input holds n elements")
+		}
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	pinned := func(p unsafe.Pointer) unsafe.Pointer {
+		if p != nil {
+			pin.Pin(p)
+		}
+		return p
+	}
+	in := C.gm_plonk_quotient_in{
+		n:  C.size_t(q.N),
+		ql: devAt(q.Ql, 0), qr: devAt(q.Qr, 0), qm: devAt(q.Qm, 0), qo: devAt(q.Qo, 0), qk: devAt(q.Qk, 0),
+		s1: devAt(q.S1, 0), s2: devAt(q.S2, 0), s3: devAt(q.S3, 0),
+		l: devAt(q.L, 0), r: devAt(q.R, 0), o: devAt(q.O, 0), z: devAt(q.Z, 0),
+		nb_bsb: C.size_t(len(q.Qcp)),
+		bl:     pinned(q.Bl), br: pinned(q.Br), bo: pinned(q.Bo), bz: pinned(q.Bz),
+		alpha: pinned(q.Alpha), beta: pinned(q.Beta), gamma: pinned(q.Gamma),
+	}
+	if len(q.Qcp) > 0 {
+		for i := range q.Qcp {
+			if q.Qcp[i] == nil || q.Pi2[i] == nil || q.Qcp[i].n != q.N || q.Pi2[i].n != q.N {
+				return errors.New("gnark_mi355x: every quotient input holds n elements")
+			}
+		}
+		qcp, _ := polyTable(q.Qcp)
+		pi2, _ := polyTable(q.Pi2)
+		in.qcp = (*unsafe.Pointer)(pinned(unsafe.Pointer(&qcp[0])))
+		in.pi2 = (*unsafe.Pointer)(pinned(unsafe.Pointer(&pi2[0])))
+	}
+	if rc := C.gm_plonk_quotient(ctx0, C.int(curve), &in, devAt(h, 0)); rc != C.GM_OK {
+		return lastErr("gm_plonk_quotient", rc)
+	}
+	return nil
+}
+
 // NTT runs an in-place fft.Domain FFT / FFTInverse of n fr.Elements at data
 // (host memory; copied to and from device 0).
 func NTT(curve int, data unsafe.Pointer, n int, inverse, dit, coset bool) error {

@@ -19,6 +19,8 @@
 //     kzg.Commit, tests/test_msm_gpu.py::test_kzg_commit_and_prepared_msm).
 //     Only gamma is derived on the host, between the two device steps.  The SRS
 //     is selected explicitly by the caller, never by pointer identity.
+//     The quotient stage as one device call (gm_plonk_quotient, resident
+//     polynomials in, h out) -> quotient; computeQuotient does not call it yet.
 //  2. Every n- and 4n-size FFT.  The domain0 ToCanonical / ToLagrange of
 //     computeNumerator (:949, :967, :1016) and of computeLinearizedPolynomial
 //     (:1301) -> toCanonical / toLagrange, and divideByZH's domain1 coset
@@ -244,6 +246,101 @@ func (d *kzgDevice) batchOpen(polys [][]fr.Element, digests []kzg.Digest, z fr.E
 		return kzg.BatchOpeningProof{}, errBatchCheck
 	}
 	hf.Reset()
+	return res, nil
+}
+
+// quotientPolys orders the fixed inputs of quotient: the selectors, the
+// permutation polynomials, the wires and Z.
+const (
+	qQl = iota
+	qQr
+	qQm
+	qQo
+	qQk
+	qS1
+	qS2
+	qS3
+	qL
+	qR
+	qO
+	qZ
+)
+
+const quotientPolys = 12
+
+var errQuotientShape = errors.New("gnark_mi355x: quotient inputs of the wrong size")
+
+// quotient runs computeNumerator + divideByZH (prove.go:771-1034, :1178-1231)
+// as one device call (gm_plonk_quotient).  polys and the BSB22 pairs qcp / pi2
+// are canonical, regular polynomials of n coefficients, l, r, o and z NOT
+// blinded; bl, br, bo (2 coefficients) and bz (3) are the blinding polynomials.
+// Returns h1, h2, h3 (n + 2 coefficients each), the slices commitToQuotient
+// commits.  StatisticalZK's randomisation of them stays with the caller.  n < 8
+// (the reference's 8n domain) is refused: the caller keeps the CPU path.
+//
+// Not yet called from computeQuotient: prove.go.diff still takes the stage one
+// transform at a time.
+func (d *kzgDevice) quotient(n int, polys [quotientPolys][]fr.Element, qcp, pi2 [][]fr.Element,
+	bl, br, bo, bz []fr.Element, alpha, beta, gamma fr.Element) ([3][]fr.Element, error) {
+	var res [3][]fr.Element
+	if n < 8 || len(qcp) != len(pi2) || len(bl) != 2 || len(br) != 2 || len(bo) != 2 || len(bz) != 3 {
+		return res, errQuotientShape
+	}
+	var devs []*gm.DevicePoly
+	defer func() {
+		for _, dp := range devs {
+			dp.Free()
+		}
+	}()
+	upload := func(p []fr.Element) (*gm.DevicePoly, error) {
+		if len(p) != n {
+			return nil, errQuotientShape
+		}
+		dp, err := gm.UploadPoly(unsafe.Pointer(&p[0]), n)
+		if err == nil {
+			devs = append(devs, dp)
+		}
+		return dp, err
+	}
+	var fixed [quotientPolys]*gm.DevicePoly
+	var err error
+	for i := range polys {
+		if fixed[i], err = upload(polys[i]); err != nil {
+			return res, err
+		}
+	}
+	in := gm.QuotientInput{
+		N:  n,
+		Ql: fixed[qQl], Qr: fixed[qQr], Qm: fixed[qQm], Qo: fixed[qQo], Qk: fixed[qQk],
+		S1: fixed[qS1], S2: fixed[qS2], S3: fixed[qS3],
+		L: fixed[qL], R: fixed[qR], O: fixed[qO], Z: fixed[qZ],
+		Bl: unsafe.Pointer(&bl[0]), Br: unsafe.Pointer(&br[0]), Bo: unsafe.Pointer(&bo[0]), Bz: unsafe.Pointer(&bz[0]),
+		Alpha: unsafe.Pointer(&alpha), Beta: unsafe.Pointer(&beta), Gamma: unsafe.Pointer(&gamma),
+	}
+	for i := range qcp {
+		var a, b *gm.DevicePoly
+		if a, err = upload(qcp[i]); err != nil {
+			return res, err
+		}
+		if b, err = upload(pi2[i]); err != nil {
+			return res, err
+		}
+		in.Qcp, in.Pi2 = append(in.Qcp, a), append(in.Pi2, b)
+	}
+	h, err := gm.AllocPoly(4 * n)
+	if err != nil {
+		return res, err
+	}
+	devs = append(devs, h)
+	if err = gm.PlonkQuotient(gm.BLS12_377, &in, h); err != nil {
+		return res, err
+	}
+	for i := range res {
+		res[i] = make([]fr.Element, n+2)
+		if err = h.Download(unsafe.Pointer(&res[i][0]), i*(n+2), n+2); err != nil {
+			return [3][]fr.Element{}, err
+		}
+	}
 	return res, nil
 }
 

@@ -35,6 +35,13 @@ func (d *kzgDevice) batchOpen([][]fr.Element, []kzg.Digest, fr.Element, hash.Has
 	return kzg.BatchOpeningProof{}, errNoGPU
 }
 
+const quotientPolys = 12
+
+func (d *kzgDevice) quotient(int, [quotientPolys][]fr.Element, [][]fr.Element, [][]fr.Element,
+	[]fr.Element, []fr.Element, []fr.Element, []fr.Element, fr.Element, fr.Element, fr.Element) ([3][]fr.Element, error) {
+	return [3][]fr.Element{}, errNoGPU
+}
+
 func (d *kzgDevice) toCanonical(*iop.Polynomial, *fft.Domain) bool { return false }
 func (d *kzgDevice) toLagrange(*iop.Polynomial, *fft.Domain) bool  { return false }
 
