@@ -12,6 +12,7 @@
 #include "groth16.hpp"
 #include "kzg.hpp"
 #include "plonk.hpp"
+#include "plonk_perm.hpp"
 #include "msm.hpp"
 #include "ntt.hpp"
 #include "runtime.hpp"
@@ -866,6 +867,25 @@ int gm_plonk_quotient(gm_ctx* ctx, int curve, const gm_plonk_quotient_in* in, vo
     ProfScope ps(ctx, "plonk_quotient_call");
     rc = curve == GM_BN254 ? plonk_quotient_device<CurveBN254>(ctx, in, h_dev)
                            : plonk_quotient_device<CurveBLS12377>(ctx, in, h_dev);
+  }
+  // also after a refusal part-way: nothing queued may outlive the call's workspace
+  GM_HIP(hipStreamSynchronize(ctx->stream));
+  prof_collect(ctx);
+  return rc;
+}
+
+// ---- PLONK permutation polynomial Z on resident wires (plonk_perm.hip) --------------
+int gm_plonk_perm_z(gm_ctx* ctx, int curve, const gm_plonk_perm_in* in, void* z_lagrange_dev,
+                    void* z_canonical_dev) {
+  if (!ctx || !in || !z_lagrange_dev) return GM_ERR_INVALID;
+  if (int rc = check_curve(curve)) return rc;
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  int rc;
+  {
+    ProfScope ps(ctx, "plonk_perm_z_call");
+    rc = curve == GM_BN254 ? plonk_perm_z_device<CurveBN254>(ctx, in, z_lagrange_dev, z_canonical_dev)
+                           : plonk_perm_z_device<CurveBLS12377>(ctx, in, z_lagrange_dev, z_canonical_dev);
   }
   // also after a refusal part-way: nothing queued may outlive the call's workspace
   GM_HIP(hipStreamSynchronize(ctx->stream));

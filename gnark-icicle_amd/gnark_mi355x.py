@@ -44,7 +44,7 @@ SYMBOLS = [
     "gm_set_msm_window", "gm_set_msm_glv", "gm_set_msm_piece_len", "gm_malloc", "gm_free", "gm_copy_to_device", "gm_memcpy_h2d",
     "gm_memcpy_d2h", "gm_memcpy_d2d", "gm_copy_points_to_device", "gm_msm", "gm_msm_host_scalars", "gm_points_upload", "gm_msm_prepared", "gm_precompute_layout", "gm_points_upload_precomputed",
     "gm_msm_precomputed", "gm_kzg_commit", "gm_kzg_eval", "gm_poly_div_linear", "gm_poly_fold", "gm_kzg_open",
-    "gm_kzg_batch_open", "gm_plonk_quotient", "gm_ntt",
+    "gm_kzg_batch_open", "gm_plonk_quotient", "gm_plonk_perm_z", "gm_ntt",
     "gm_poly_ops", "gm_reverse_scalars", "gm_groth16_compute_h", "gm_g16_pk_upload", "gm_g16_pk_upload_ex", "gm_g16_pk_upload_shard",
     "gm_g16_partial_bytes", "gm_g16_prove_partial", "gm_g16_finish",
     "gm_g16_pk_free", "gm_g16_pk_precomputed", "gm_g16_prove", "gm_g16_prove_device", "gm_jac_add", "gm_jac_to_affine",
@@ -74,6 +74,18 @@ class _PlonkQuotientIn(ctypes.Structure):
                 + [("nb_bsb", ctypes.c_size_t), ("qcp", ctypes.POINTER(ctypes.c_void_p)),
                    ("pi2", ctypes.POINTER(ctypes.c_void_p))]
                 + [(k, ctypes.c_void_p) for k in ("bl", "br", "bo", "bz", "alpha", "beta", "gamma")])
+
+
+PLONK_PERM_POLYS = ("l", "r", "o", "s1", "s2", "s3")
+# geometry of the scan behind gm_plonk_perm_z (csrc/plonk_perm.hpp): rows per
+# thread run, rows per chunk, chunks per tile of the carry scan
+PLONK_PERM_E, PLONK_PERM_CHUNK, PLONK_PERM_CARRY_TILE = 4, 512, 64
+
+
+class _PlonkPermIn(ctypes.Structure):
+    """gm_plonk_perm_in (include/gnark_mi355x.h)."""
+    _fields_ = ([("n", ctypes.c_size_t)] + [(k, ctypes.c_void_p) for k in PLONK_PERM_POLYS]
+                + [("beta", ctypes.c_void_p), ("gamma", ctypes.c_void_p)])
 
 
 _lib = None
@@ -143,6 +155,7 @@ def load_library(path: str = LIB_PATH):
     L.gm_kzg_open.argtypes = [vp, i, vp, sz, vp, sz, vp, vp, vp]
     L.gm_kzg_batch_open.argtypes = [vp, i, vp, sz, pvp, psz, sz, vp, vp, vp, vp]
     L.gm_plonk_quotient.argtypes = [vp, i, ctypes.POINTER(_PlonkQuotientIn), vp]
+    L.gm_plonk_perm_z.argtypes = [vp, i, ctypes.POINTER(_PlonkPermIn), vp, vp]
     L.gm_ntt.argtypes = [vp, i, vp, sz, i, i, i]
     L.gm_poly_ops.argtypes = [vp, i, vp, vp, vp, sz, vp]
     L.gm_reverse_scalars.argtypes = [vp, i, vp, sz]
@@ -488,6 +501,23 @@ class Context:
         for k, v in zip(("bl", "br", "bo", "bz", "alpha", "beta", "gamma"), keep):
             setattr(a, k, v.ctypes.data)
         _check(load_library().gm_plonk_quotient(self.handle, curve_id(curve), ctypes.byref(a), h.ptr))
+
+    # ---- PLONK permutation polynomial Z on resident wires ------------------------
+    def plonk_perm_z(self, curve, n: int, polys: dict, beta: bytes, gamma: bytes, z_lagrange: DeviceBuffer,
+                     z_canonical: DeviceBuffer = None):
+        """gm_plonk_perm_z: z_lagrange <- the copy-constraint accumulator Z (n
+        elements, Lagrange regular); z_canonical, if given, <- the same polynomial
+        in canonical regular form.  polys: DeviceBuffers keyed by PLONK_PERM_POLYS
+        (n elements each, Lagrange regular; None passes a NULL pointer)."""
+        a = _PlonkPermIn()
+        a.n = n
+        for k in PLONK_PERM_POLYS:
+            setattr(a, k, polys[k].ptr if polys[k] is not None else None)
+        keep = [_buf(beta), _buf(gamma)]
+        a.beta, a.gamma = keep[0].ctypes.data, keep[1].ctypes.data
+        _check(load_library().gm_plonk_perm_z(self.handle, curve_id(curve), ctypes.byref(a),
+                                              z_lagrange.ptr if z_lagrange is not None else None,
+                                              z_canonical.ptr if z_canonical is not None else None))
 
     def msm_on_device(self, scalars, points, n, curve="bn254"):
         """MsmOnDevice(scalars_d, points_d, count, convert=true) -> G1Jac bytes."""

@@ -247,6 +247,44 @@ typedef struct {
 } gm_plonk_quotient_in;
 int gm_plonk_quotient(gm_ctx* ctx, int curve, const gm_plonk_quotient_in* in, void* h_dev);
 
+/* ---- PLONK permutation polynomial Z (backend/plonk/bls12-377/prove.go:565-597
+ *      buildRatioCopyConstraint, gnark-crypto iop.BuildRatioCopyConstraint) --------
+ * The copy-constraint accumulator on polynomials resident on the device.  Every
+ * device input is n Montgomery fr.Elements, 16-byte aligned, and is left unchanged:
+ *  - l, r, o: Lagrange basis, regular order (element i is the value at w^i);
+ *  - s1, s2, s3: Lagrange basis, regular order, s_k[i] = id[sigma(k n + i)] (gnark's
+ *    trace.S1..S3 at setup), with the identity support id[k n + i] = g^k w^i,
+ *    g = FrMultiplicativeGen (5 for BN254, 22 for BLS12-377), w the generator of
+ *    fft.NewDomain(n).
+ * beta and gamma are single host elements.  For i in [0, n - 1):
+ *   num_i = (l[i] + beta w^i + gamma)(r[i] + beta g w^i + gamma)(o[i] + beta g^2 w^i + gamma)
+ *   den_i = (l[i] + beta s1[i] + gamma)(r[i] + beta s2[i] + gamma)(o[i] + beta s3[i] + gamma)
+ *   N_i = prod_{j<=i} num_j,   D_i = prod_{j<=i} den_j
+ *   Z[0] = 1,   Z[i+1] = N_i inv0(D_i),   inv0(0) = 0, otherwise the field inverse
+ * (BuildRatioCopyConstraint followed by fr.BatchInvert, which leaves zero entries
+ * zero): from the first zero denominator on every later Z value is 0, the values
+ * before it are unaffected.  Row n - 1 does not enter the product.
+ *
+ * z_lagrange_dev receives Z as n elements, Lagrange regular: it can go into
+ * gm_msm_prepared over the Lagrange SRS where it lies.  z_canonical_dev, if not
+ * NULL, receives the same polynomial in the canonical basis, regular order, NOT
+ * blinded: the z member of gm_plonk_quotient_in.  Every stored element is fully
+ * reduced, so the bytes are gnark's.  The outputs must overlap no input and must
+ * not overlap each other.
+ *
+ * GM_ERR_INVALID: NULL context or NULL struct (both checked before any device
+ * call), a NULL required pointer, n not a power of two or n < 8, a misaligned
+ * pointer, an overlap.  Scratch (four elements per chunk of 512 rows) comes from
+ * the context's workspace; gm_trim releases it. */
+typedef struct {
+  size_t n;                    /* power of two, >= 8 (as gm_plonk_quotient) */
+  const void *l, *r, *o;       /* device, Lagrange regular */
+  const void *s1, *s2, *s3;    /* device, Lagrange regular */
+  const void *beta, *gamma;    /* host, 1 Fr each */
+} gm_plonk_perm_in;
+int gm_plonk_perm_z(gm_ctx* ctx, int curve, const gm_plonk_perm_in* in,
+                    void* z_lagrange_dev, void* z_canonical_dev /* may be NULL */);
+
 /* ---- NTT (iciclegnark GenerateTwiddleFactors icicle.go:68,73;
  *      INttOnDevice :489,502; NttOnDevice :490; PolyOps :500;
  *      ReverseScalars :510; CPU twin fft.Domain.FFT/FFTInverse

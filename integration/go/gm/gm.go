@@ -654,6 +654,54 @@ func PlonkQuotient(curve int, q *QuotientInput, h *DevicePoly) error {
 	return nil
 }
 
+// PermInput mirrors gm_plonk_perm_in.  L, R, O and S1, S2, S3 are n fr.Elements
+// each in Lagrange basis, regular order, resident on the device (S1..S3 as
+// trace.S1..S3 are at setup); Beta and Gamma (1 fr.Element) point at host memory.
+type PermInput struct {
+	N                   int
+	L, R, O, S1, S2, S3 *DevicePoly
+	Beta, Gamma         unsafe.Pointer
+}
+
+// PlonkPermZ leaves the copy-constraint accumulator Z (p.N fr.Elements, Lagrange,
+// regular) in zLagrange and, if zCanonical is not nil, the same polynomial in
+// canonical regular form there: buildRatioCopyConstraint (prove.go:565-597) on
+// resident wires.  cgo rule as for PlonkQuotient: &in is a Go pointer handed to C,
+// so the two host pointers stored in it are pinned for the call; the other members
+// are device addresses.
+func PlonkPermZ(curve int, p *PermInput, zLagrange, zCanonical *DevicePoly) error {
+	if zLagrange == nil || zLagrange.n < p.N || (zCanonical != nil && zCanonical.n < p.N) {
+		return errors.New("gnark_mi355x: Z needs n elements")
+	}
+	for _, q := range []*DevicePoly{p.L, p.R, p.O, p.S1, p.S2, p.S3} {
+		if q == nil || q.n != p.N {
+			return errors.New("gnark_mi355x: every permutation input holds n elements")
+		}
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	pinned := func(q unsafe.Pointer) unsafe.Pointer {
+		if q != nil {
+			pin.Pin(q)
+		}
+		return q
+	}
+	in := C.gm_plonk_perm_in{
+		n: C.size_t(p.N),
+		l: devAt(p.L, 0), r: devAt(p.R, 0), o: devAt(p.O, 0),
+		s1: devAt(p.S1, 0), s2: devAt(p.S2, 0), s3: devAt(p.S3, 0),
+		beta: pinned(p.Beta), gamma: pinned(p.Gamma),
+	}
+	var zc unsafe.Pointer
+	if zCanonical != nil {
+		zc = devAt(zCanonical, 0)
+	}
+	if rc := C.gm_plonk_perm_z(ctx0, C.int(curve), &in, devAt(zLagrange, 0), zc); rc != C.GM_OK {
+		return lastErr("gm_plonk_perm_z", rc)
+	}
+	return nil
+}
+
 // NTT runs an in-place fft.Domain FFT / FFTInverse of n fr.Elements at data
 // (host memory; copied to and from device 0).
 func NTT(curve int, data unsafe.Pointer, n int, inverse, dit, coset bool) error {

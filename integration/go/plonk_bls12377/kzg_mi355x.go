@@ -21,6 +21,10 @@
 //     is selected explicitly by the caller, never by pointer identity.
 //     The quotient stage as one device call (gm_plonk_quotient, resident
 //     polynomials in, h out) -> quotient; computeQuotient does not call it yet.
+//     The copy-constraint accumulator Z as one device call (gm_plonk_perm_z:
+//     ratios, scan, one inversion) with its commitment over the Lagrange SRS read
+//     where Z lies -> ratioZ; buildRatioCopyConstraint (:565-597) does not call it
+//     yet.
 //  2. Every n- and 4n-size FFT.  The domain0 ToCanonical / ToLagrange of
 //     computeNumerator (:949, :967, :1016) and of computeLinearizedPolynomial
 //     (:1301) -> toCanonical / toLagrange, and divideByZH's domain1 coset
@@ -342,6 +346,73 @@ func (d *kzgDevice) quotient(n int, polys [quotientPolys][]fr.Element, qcp, pi2 
 		}
 	}
 	return res, nil
+}
+
+var errRatioShape = errors.New("gnark_mi355x: permutation inputs of the wrong size")
+
+// ratioZ runs buildRatioCopyConstraint (prove.go:565-597: iop's
+// BuildRatioCopyConstraint and the commitment of Z over the Lagrange SRS) as one
+// device call and one MSM on the resident result (gm_plonk_perm_z,
+// gm_msm_prepared).  l, r, o are the solved wires and s1, s2, s3 the trace's
+// permutation polynomials, all n values in Lagrange basis, regular order.  Returns
+// Z in Lagrange form, Z in canonical form (not blinded: the z of quotient) and the
+// commitment of the Lagrange form.  n < 8 is refused: the caller keeps the CPU
+// path.
+//
+// Not yet called from buildRatioCopyConstraint: prove.go.diff still builds Z
+// with iop on the host.
+func (d *kzgDevice) ratioZ(n int, l, r, o, s1, s2, s3 []fr.Element, beta, gamma fr.Element) ([]fr.Element,
+	[]fr.Element, kzg.Digest, error) {
+	if n < 8 || n > d.nLagr {
+		return nil, nil, kzg.Digest{}, errRatioShape
+	}
+	var devs []*gm.DevicePoly
+	defer func() {
+		for _, dp := range devs {
+			dp.Free()
+		}
+	}()
+	var in [6]*gm.DevicePoly
+	for i, p := range [6][]fr.Element{l, r, o, s1, s2, s3} {
+		if len(p) != n {
+			return nil, nil, kzg.Digest{}, errRatioShape
+		}
+		dp, err := gm.UploadPoly(unsafe.Pointer(&p[0]), n)
+		if err != nil {
+			return nil, nil, kzg.Digest{}, err
+		}
+		devs = append(devs, dp)
+		in[i] = dp
+	}
+	var out [2]*gm.DevicePoly
+	for i := range out {
+		dp, err := gm.AllocPoly(n)
+		if err != nil {
+			return nil, nil, kzg.Digest{}, err
+		}
+		devs = append(devs, dp)
+		out[i] = dp
+	}
+	perm := gm.PermInput{
+		N: n,
+		L: in[0], R: in[1], O: in[2], S1: in[3], S2: in[4], S3: in[5],
+		Beta: unsafe.Pointer(&beta), Gamma: unsafe.Pointer(&gamma),
+	}
+	if err := gm.PlonkPermZ(gm.BLS12_377, &perm, out[0], out[1]); err != nil {
+		return nil, nil, kzg.Digest{}, err
+	}
+	var digest curve.G1Affine
+	if err := d.lagr.CommitResident(out[0], 0, n, unsafe.Pointer(&digest)); err != nil {
+		return nil, nil, kzg.Digest{}, err
+	}
+	zl, zc := make([]fr.Element, n), make([]fr.Element, n)
+	if err := out[0].Download(unsafe.Pointer(&zl[0]), 0, n); err != nil {
+		return nil, nil, kzg.Digest{}, err
+	}
+	if err := out[1].Download(unsafe.Pointer(&zc[0]), 0, n); err != nil {
+		return nil, nil, kzg.Digest{}, err
+	}
+	return zl, zc, digest, nil
 }
 
 // plainForm: a Lagrange or Canonical (not coset) polynomial of |dom|

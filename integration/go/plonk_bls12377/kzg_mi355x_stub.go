@@ -42,6 +42,11 @@ func (d *kzgDevice) quotient(int, [quotientPolys][]fr.Element, [][]fr.Element, [
 	return [3][]fr.Element{}, errNoGPU
 }
 
+func (d *kzgDevice) ratioZ(int, []fr.Element, []fr.Element, []fr.Element, []fr.Element, []fr.Element, []fr.Element,
+	fr.Element, fr.Element) ([]fr.Element, []fr.Element, kzg.Digest, error) {
+	return nil, nil, kzg.Digest{}, errNoGPU
+}
+
 func (d *kzgDevice) toCanonical(*iop.Polynomial, *fft.Domain) bool { return false }
 func (d *kzgDevice) toLagrange(*iop.Polynomial, *fft.Domain) bool  { return false }
 
