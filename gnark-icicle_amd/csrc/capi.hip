@@ -12,6 +12,7 @@
 #include "groth16.hpp"
 #include "kzg.hpp"
 #include "plonk.hpp"
+#include "plonk_lin.hpp"
 #include "plonk_perm.hpp"
 #include "msm.hpp"
 #include "ntt.hpp"
@@ -886,6 +887,24 @@ int gm_plonk_perm_z(gm_ctx* ctx, int curve, const gm_plonk_perm_in* in, void* z_
     ProfScope ps(ctx, "plonk_perm_z_call");
     rc = curve == GM_BN254 ? plonk_perm_z_device<CurveBN254>(ctx, in, z_lagrange_dev, z_canonical_dev)
                            : plonk_perm_z_device<CurveBLS12377>(ctx, in, z_lagrange_dev, z_canonical_dev);
+  }
+  // also after a refusal part-way: nothing queued may outlive the call's workspace
+  GM_HIP(hipStreamSynchronize(ctx->stream));
+  prof_collect(ctx);
+  return rc;
+}
+
+// ---- PLONK linearized polynomial on resident buffers (plonk_lin.hip) ----------------
+int gm_plonk_linearize(gm_ctx* ctx, int curve, const gm_plonk_linearize_in* in, const gm_plonk_linearize_out* out) {
+  if (!ctx || !in || !out) return GM_ERR_INVALID;
+  if (int rc = check_curve(curve)) return rc;
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  int rc;
+  {
+    ProfScope ps(ctx, "plonk_linearize_call");
+    rc = curve == GM_BN254 ? plonk_linearize_device<CurveBN254>(ctx, in, out)
+                           : plonk_linearize_device<CurveBLS12377>(ctx, in, out);
   }
   // also after a refusal part-way: nothing queued may outlive the call's workspace
   GM_HIP(hipStreamSynchronize(ctx->stream));

@@ -44,7 +44,7 @@ SYMBOLS = [
     "gm_set_msm_window", "gm_set_msm_glv", "gm_set_msm_piece_len", "gm_malloc", "gm_free", "gm_copy_to_device", "gm_memcpy_h2d",
     "gm_memcpy_d2h", "gm_memcpy_d2d", "gm_copy_points_to_device", "gm_msm", "gm_msm_host_scalars", "gm_points_upload", "gm_msm_prepared", "gm_precompute_layout", "gm_points_upload_precomputed",
     "gm_msm_precomputed", "gm_kzg_commit", "gm_kzg_eval", "gm_poly_div_linear", "gm_poly_fold", "gm_kzg_open",
-    "gm_kzg_batch_open", "gm_plonk_quotient", "gm_plonk_perm_z", "gm_ntt",
+    "gm_kzg_batch_open", "gm_plonk_quotient", "gm_plonk_perm_z", "gm_plonk_linearize", "gm_ntt",
     "gm_poly_ops", "gm_reverse_scalars", "gm_groth16_compute_h", "gm_g16_pk_upload", "gm_g16_pk_upload_ex", "gm_g16_pk_upload_shard",
     "gm_g16_partial_bytes", "gm_g16_prove_partial", "gm_g16_finish",
     "gm_g16_pk_free", "gm_g16_pk_precomputed", "gm_g16_prove", "gm_g16_prove_device", "gm_jac_add", "gm_jac_to_affine",
@@ -86,6 +86,26 @@ class _PlonkPermIn(ctypes.Structure):
     """gm_plonk_perm_in (include/gnark_mi355x.h)."""
     _fields_ = ([("n", ctypes.c_size_t)] + [(k, ctypes.c_void_p) for k in PLONK_PERM_POLYS]
                 + [("beta", ctypes.c_void_p), ("gamma", ctypes.c_void_p)])
+
+
+# geometry of the combination pass behind gm_plonk_linearize (csrc/plonk_lin.hpp):
+# coefficients per block; a lane owns one coefficient and the grid is not capped
+PLONK_LIN_BLOCK = 256
+PLONK_LIN_BLINDED = ("l_blinded", "r_blinded", "o_blinded", "z_blinded")
+
+
+class _PlonkLinearizeIn(ctypes.Structure):
+    """gm_plonk_linearize_in (include/gnark_mi355x.h)."""
+    _fields_ = ([("n", ctypes.c_size_t)] + [(k, ctypes.c_void_p) for k in PLONK_POLYS]
+                + [("nb_bsb", ctypes.c_size_t), ("qcp", ctypes.POINTER(ctypes.c_void_p)),
+                   ("pi2", ctypes.POINTER(ctypes.c_void_p))]
+                + [(k, ctypes.c_void_p) for k in ("bl", "br", "bo", "bz", "h", "h_rand", "alpha", "beta", "gamma",
+                                                  "zeta")])
+
+
+class _PlonkLinearizeOut(ctypes.Structure):
+    """gm_plonk_linearize_out (include/gnark_mi355x.h)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("lin",) + PLONK_LIN_BLINDED + ("evals",)]
 
 
 _lib = None
@@ -156,6 +176,7 @@ def load_library(path: str = LIB_PATH):
     L.gm_kzg_batch_open.argtypes = [vp, i, vp, sz, pvp, psz, sz, vp, vp, vp, vp]
     L.gm_plonk_quotient.argtypes = [vp, i, ctypes.POINTER(_PlonkQuotientIn), vp]
     L.gm_plonk_perm_z.argtypes = [vp, i, ctypes.POINTER(_PlonkPermIn), vp, vp]
+    L.gm_plonk_linearize.argtypes = [vp, i, ctypes.POINTER(_PlonkLinearizeIn), ctypes.POINTER(_PlonkLinearizeOut)]
     L.gm_ntt.argtypes = [vp, i, vp, sz, i, i, i]
     L.gm_poly_ops.argtypes = [vp, i, vp, vp, vp, sz, vp]
     L.gm_reverse_scalars.argtypes = [vp, i, vp, sz]
@@ -518,6 +539,45 @@ class Context:
         _check(load_library().gm_plonk_perm_z(self.handle, curve_id(curve), ctypes.byref(a),
                                               z_lagrange.ptr if z_lagrange is not None else None,
                                               z_canonical.ptr if z_canonical is not None else None))
+
+    # ---- PLONK linearized polynomial on resident buffers --------------------------
+    def plonk_linearize(self, curve, n: int, polys: dict, qcp, pi2, blinds: dict, h: DeviceBuffer, alpha: bytes,
+                        beta: bytes, gamma: bytes, zeta: bytes, lin: DeviceBuffer, h_rand: bytes = None,
+                        blinded: dict = None) -> list:
+        """gm_plonk_linearize: lin <- the linearized polynomial (n + 3 elements);
+        returns [l~(zeta), r~(zeta), o~(zeta), s1(zeta), s2(zeta), z~(w zeta), qcp_j(zeta)...]
+        as 32-byte Montgomery elements.  polys, qcp, pi2, blinds as plonk_quotient
+        (a None in polys passes a NULL pointer); h: the quotient's 4n elements;
+        h_rand: two elements (StatisticalZK) or None; blinded: DeviceBuffers keyed
+        by PLONK_LIN_BLINDED (n + 2 elements, z_blinded n + 3), any of them absent."""
+        a = _PlonkLinearizeIn()
+        a.n = n
+        for k in PLONK_POLYS:
+            setattr(a, k, polys[k].ptr if polys[k] is not None else None)
+        nb = max(len(qcp) if qcp is not None else 0, len(pi2) if pi2 is not None else 0)
+        a.nb_bsb = nb
+        tabs = []
+        for name, t in (("qcp", qcp), ("pi2", pi2)):
+            if t is not None and nb:
+                arr = (ctypes.c_void_p * nb)(*[None if b is None else b.ptr for b in t])
+                tabs.append(arr)
+                setattr(a, name, ctypes.cast(arr, ctypes.POINTER(ctypes.c_void_p)))
+        keep = {k: _buf(v) for k, v in (("bl", blinds["bl"]), ("br", blinds["br"]), ("bo", blinds["bo"]),
+                                        ("bz", blinds["bz"]), ("h_rand", h_rand), ("alpha", alpha), ("beta", beta),
+                                        ("gamma", gamma), ("zeta", zeta)) if v is not None}
+        for k, v in keep.items():
+            setattr(a, k, v.ctypes.data)
+        a.h = h.ptr if h is not None else None
+        o = _PlonkLinearizeOut()
+        o.lin = lin.ptr if lin is not None else None
+        for k in PLONK_LIN_BLINDED:
+            b = (blinded or {}).get(k)
+            setattr(o, k, b.ptr if b is not None else None)
+        ev = np.zeros(FR_BYTES * (6 + nb), np.uint8)
+        o.evals = ev.ctypes.data
+        _check(load_library().gm_plonk_linearize(self.handle, curve_id(curve), ctypes.byref(a), ctypes.byref(o)))
+        b = ev.tobytes()
+        return [b[FR_BYTES * j:FR_BYTES * (j + 1)] for j in range(6 + nb)]
 
     def msm_on_device(self, scalars, points, n, curve="bn254"):
         """MsmOnDevice(scalars_d, points_d, count, convert=true) -> G1Jac bytes."""

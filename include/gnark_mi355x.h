@@ -285,6 +285,74 @@ typedef struct {
 int gm_plonk_perm_z(gm_ctx* ctx, int curve, const gm_plonk_perm_in* in,
                     void* z_lagrange_dev, void* z_canonical_dev /* may be NULL */);
 
+/* ---- PLONK linearized polynomial (backend/plonk/bls12-377/prove.go:656-724
+ *      computeLinearizedPolynomial, :1233-1368 innerComputeLinearizedPoly) --------
+ * The last polynomial stage of the prover on buffers resident on the device: the
+ * evaluations at zeta, the linearized polynomial r(X) and, where asked for, the
+ * blinded wires and Z~, so that the commit of r(X) (gm_msm_prepared), the opening
+ * of Z~ at w zeta (gm_kzg_open) and the batch opening at zeta (gm_kzg_eval,
+ * gm_kzg_batch_open) run where the data lie.
+ *
+ * The first twenty members of the input are gm_plonk_quotient_in's (same
+ * conventions: canonical basis, regular order, n Montgomery fr.Elements each,
+ * 16-byte aligned, l, r, o, z NOT blinded, qk the completed Qk); h is
+ * gm_plonk_quotient's h_dev (4n elements, of which h[0 .. 3(n + 2)) are read);
+ * h_rand, if not NULL, holds the two StatisticalZK randomizers of the quotient
+ * shards (prove.go:619-654).  Every input is left unchanged.
+ *
+ * With g = FrMultiplicativeGen, w the generator of fft.NewDomain(n), m = n + 2,
+ * Z_H(zeta) = zeta^n - 1 and P~ = P + (X^n - 1) b (as coefficients
+ * getBlindedCoefficients, prove.go:1103-1111: P~[i] = P[i] - b[i] for i < len(b),
+ * P~[n + i] = b[i]), evals receives, in this order,
+ *   l~(zeta), r~(zeta), o~(zeta), s1(zeta), s2(zeta), z~(w zeta), qcp_j(zeta) (j < nb_bsb)
+ * (the blinded ones as evaluateBlinded, :1073-1100), and with
+ *   rl  = l~(zeta) r~(zeta)
+ *   c1  = alpha (l~(zeta) + beta s1(zeta) + gamma)(r~(zeta) + beta s2(zeta) + gamma) beta z~(w zeta)
+ *   c2  = -alpha (l~(zeta) + beta zeta + gamma)(r~(zeta) + beta g zeta + gamma)(o~(zeta) + beta g^2 zeta + gamma)
+ *   a2L = alpha^2 (zeta^n - 1) inv0(zeta - 1) / n      (inv0(0) = 0: 0 at zeta = 1)
+ *   zm  = zeta^m,   zh = zeta^n - 1
+ * lin receives, for i in [0, n + 3), every polynomial contributing 0 at and past
+ * its own length,
+ *   lin[i] = (c2 + a2L) z~[i]
+ *          + c1 s3[i] + rl qm[i] + l~(zeta) ql[i] + r~(zeta) qr[i] + o~(zeta) qo[i] + qk[i]
+ *          + sum_j qcp_j(zeta) pi2_j[i]                                  (all of these: i < n)
+ *          - zh (h[i] + zm h[m + i] + zm^2 h[2m + i])                    (i < m)
+ * and, with h_rand = (rho0, rho1), lin[0] gains zh (zm rho0 + zm^2 rho1) and
+ * lin[m] gains -zh (rho0 + zm rho1).  This is innerComputeLinearizedPoly's return
+ * value byte for byte: every stored element is fully reduced.  l_blinded,
+ * r_blinded, o_blinded (n + 2 elements) and z_blinded (n + 3), each of which may
+ * be NULL, receive the blinded coefficient lists.
+ *
+ * GM_ERR_INVALID: NULL context, NULL in or NULL out (all checked before any
+ * device call), a NULL required pointer, n not a power of two or n < 8,
+ * nb_bsb > 0 with a NULL table or entry, a misaligned device pointer, an output
+ * overlapping an input or another output.  nb_bsb is not capped.  Scratch (the
+ * evaluations' chunk sums and nb_bsb table entries) comes from the context's
+ * workspace; gm_trim releases it. */
+typedef struct {
+  size_t n;                                   /* domain0 size: power of two, >= 8 */
+  const void *ql, *qr, *qm, *qo, *qk, *s1, *s2, *s3;  /* device, n Fr each (qk = completed Qk) */
+  const void *l, *r, *o, *z;                  /* device, n Fr each, NOT blinded */
+  size_t nb_bsb;                              /* may be 0; not capped */
+  const void* const* qcp;                     /* host array of nb_bsb device pointers */
+  const void* const* pi2;                     /* host array of nb_bsb device pointers */
+  const void *bl, *br, *bo;                   /* host, 2 Fr each */
+  const void *bz;                             /* host, 3 Fr */
+  const void *h;                              /* device, 4n Fr: gm_plonk_quotient's h_dev */
+  const void *h_rand;                         /* host, 2 Fr (StatisticalZK randomizers) or NULL */
+  const void *alpha, *beta, *gamma, *zeta;    /* host, 1 Fr each */
+} gm_plonk_linearize_in;
+
+typedef struct {
+  void *lin;                                  /* device, n + 3 Fr, required */
+  void *l_blinded, *r_blinded, *o_blinded;    /* device, n + 2 Fr each, each may be NULL */
+  void *z_blinded;                            /* device, n + 3 Fr, may be NULL */
+  void *evals;                                /* host, 6 + nb_bsb Fr, required */
+} gm_plonk_linearize_out;
+
+int gm_plonk_linearize(gm_ctx* ctx, int curve, const gm_plonk_linearize_in* in,
+                       const gm_plonk_linearize_out* out);
+
 /* ---- NTT (iciclegnark GenerateTwiddleFactors icicle.go:68,73;
  *      INttOnDevice :489,502; NttOnDevice :490; PolyOps :500;
  *      ReverseScalars :510; CPU twin fft.Domain.FFT/FFTInverse

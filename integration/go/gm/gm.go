@@ -702,6 +702,111 @@ func PlonkPermZ(curve int, p *PermInput, zLagrange, zCanonical *DevicePoly) erro
 	return nil
 }
 
+// LinearizeInput mirrors gm_plonk_linearize_in: the members of QuotientInput (same
+// conventions; Qk is the completed Qk), the quotient H (4 N fr.Elements, the h of
+// PlonkQuotient), HRand (2 fr.Elements in host memory, StatisticalZK's shard
+// randomizers, or nil) and Zeta (1 fr.Element in host memory).
+type LinearizeInput struct {
+	N                              int
+	Ql, Qr, Qm, Qo, Qk, S1, S2, S3 *DevicePoly
+	L, R, O, Z                     *DevicePoly
+	Qcp, Pi2                       []*DevicePoly
+	Bl, Br, Bo, Bz                 unsafe.Pointer
+	H                              *DevicePoly
+	HRand                          unsafe.Pointer
+	Alpha, Beta, Gamma, Zeta       unsafe.Pointer
+}
+
+// LinearizeOutput mirrors gm_plonk_linearize_out.  Lin (N + 3 fr.Elements) is
+// required; LBlinded, RBlinded, OBlinded (N + 2) and ZBlinded (N + 3) may each be
+// nil.  Evals points at 6 + len(Qcp) fr.Elements in host memory: l~(zeta),
+// r~(zeta), o~(zeta), s1(zeta), s2(zeta), z~(w zeta), qcp_j(zeta).
+type LinearizeOutput struct {
+	Lin                          *DevicePoly
+	LBlinded, RBlinded, OBlinded *DevicePoly
+	ZBlinded                     *DevicePoly
+	Evals                        unsafe.Pointer
+}
+
+// PlonkLinearize runs computeLinearizedPolynomial / innerComputeLinearizedPoly
+// (prove.go:656-724, :1233-1368) on resident polynomials: the evaluations at zeta,
+// the linearized polynomial and, where asked for, the blinded wires and Z~ are left
+// on the device for the commit and the openings that follow.  cgo rule as for
+// PlonkQuotient: &in and &out are Go pointers handed to C, so the host pointers
+// stored in them and the two address tables are pinned for the call; every other
+// member is a device address.
+func PlonkLinearize(curve int, q *LinearizeInput, o *LinearizeOutput) error {
+	if len(q.Qcp) != len(q.Pi2) {
+		return errors.New("gnark_mi355x: qcp and pi2 differ in length")
+	}
+	if q.H == nil || q.H.n < 4*q.N {
+		return errors.New("gnark_mi355x: the quotient holds 4n elements")
+	}
+	for _, p := range []*DevicePoly{q.Ql, q.Qr, q.Qm, q.Qo, q.Qk, q.S1, q.S2, q.S3, q.L, q.R, q.O, q.Z} {
+		if p == nil || p.n != q.N {
+			return errors.New("gnark_mi355x: every linearization input holds n elements")
+		}
+	}
+	if o.Lin == nil || o.Lin.n < q.N+3 || o.Evals == nil {
+		return errors.New("gnark_mi355x: the linearized polynomial needs n + 3 elements and the evaluations a buffer")
+	}
+	for i, p := range []*DevicePoly{o.LBlinded, o.RBlinded, o.OBlinded, o.ZBlinded} {
+		if p != nil && p.n < q.N+2+i/3 {
+			return errors.New("gnark_mi355x: a blinded output is too short")
+		}
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	pinned := func(p unsafe.Pointer) unsafe.Pointer {
+		if p != nil {
+			pin.Pin(p)
+		}
+		return p
+	}
+	in := C.gm_plonk_linearize_in{
+		n:  C.size_t(q.N),
+		ql: devAt(q.Ql, 0), qr: devAt(q.Qr, 0), qm: devAt(q.Qm, 0), qo: devAt(q.Qo, 0), qk: devAt(q.Qk, 0),
+		s1: devAt(q.S1, 0), s2: devAt(q.S2, 0), s3: devAt(q.S3, 0),
+		l: devAt(q.L, 0), r: devAt(q.R, 0), o: devAt(q.O, 0), z: devAt(q.Z, 0),
+		nb_bsb: C.size_t(len(q.Qcp)),
+		bl:     pinned(q.Bl), br: pinned(q.Br), bo: pinned(q.Bo), bz: pinned(q.Bz),
+		h:      devAt(q.H, 0),
+		h_rand: pinned(q.HRand),
+		alpha:  pinned(q.Alpha), beta: pinned(q.Beta), gamma: pinned(q.Gamma), zeta: pinned(q.Zeta),
+	}
+	if len(q.Qcp) > 0 {
+		for i := range q.Qcp {
+			if q.Qcp[i] == nil || q.Pi2[i] == nil || q.Qcp[i].n != q.N || q.Pi2[i].n != q.N {
+				return errors.New("gnark_mi355x: every linearization input holds n elements")
+			}
+		}
+		qcp, _ := polyTable(q.Qcp)
+		pi2, _ := polyTable(q.Pi2)
+		in.qcp = (*unsafe.Pointer)(pinned(unsafe.Pointer(&qcp[0])))
+		in.pi2 = (*unsafe.Pointer)(pinned(unsafe.Pointer(&pi2[0])))
+	}
+	out := C.gm_plonk_linearize_out{
+		lin:   devAt(o.Lin, 0),
+		evals: pinned(o.Evals),
+	}
+	if o.LBlinded != nil {
+		out.l_blinded = devAt(o.LBlinded, 0)
+	}
+	if o.RBlinded != nil {
+		out.r_blinded = devAt(o.RBlinded, 0)
+	}
+	if o.OBlinded != nil {
+		out.o_blinded = devAt(o.OBlinded, 0)
+	}
+	if o.ZBlinded != nil {
+		out.z_blinded = devAt(o.ZBlinded, 0)
+	}
+	if rc := C.gm_plonk_linearize(ctx0, C.int(curve), &in, &out); rc != C.GM_OK {
+		return lastErr("gm_plonk_linearize", rc)
+	}
+	return nil
+}
+
 // NTT runs an in-place fft.Domain FFT / FFTInverse of n fr.Elements at data
 // (host memory; copied to and from device 0).
 func NTT(curve int, data unsafe.Pointer, n int, inverse, dit, coset bool) error {

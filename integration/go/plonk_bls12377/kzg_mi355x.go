@@ -25,6 +25,10 @@
 //     ratios, scan, one inversion) with its commitment over the Lagrange SRS read
 //     where Z lies -> ratioZ; buildRatioCopyConstraint (:565-597) does not call it
 //     yet.
+//     The linearized polynomial as one device call (gm_plonk_linearize: the
+//     evaluations at zeta, one streaming combination) with its commitment read
+//     where it lies -> linearize; computeLinearizedPolynomial (:656-724) does not
+//     call it yet.
 //  2. Every n- and 4n-size FFT.  The domain0 ToCanonical / ToLagrange of
 //     computeNumerator (:949, :967, :1016) and of computeLinearizedPolynomial
 //     (:1301) -> toCanonical / toLagrange, and divideByZH's domain1 coset
@@ -413,6 +417,97 @@ func (d *kzgDevice) ratioZ(n int, l, r, o, s1, s2, s3 []fr.Element, beta, gamma 
 		return nil, nil, kzg.Digest{}, err
 	}
 	return zl, zc, digest, nil
+}
+
+var errLinearizeShape = errors.New("gnark_mi355x: linearization inputs of the wrong size")
+
+// linearize runs computeLinearizedPolynomial (prove.go:656-724: the evaluations
+// at zeta, innerComputeLinearizedPoly and the commitment of its result) as one
+// device call and one MSM on the resident result (gm_plonk_linearize,
+// gm_msm_prepared).  polys, qcp, pi2 and the blinding polynomials are quotient's
+// (l, r, o, z NOT blinded, Qk completed); h holds the 4n coefficients of the
+// quotient, of which the first 3 (n + 2) are read; hRand is nil or
+// StatisticalZK's two shard randomizers.  Returns the linearized polynomial
+// (n + 3 coefficients), its commitment over the canonical SRS and the evaluations
+// l~(zeta), r~(zeta), o~(zeta), s1(zeta), s2(zeta), z~(w zeta), qcp_j(zeta).  n < 8
+// is refused: the caller keeps the CPU path.
+//
+// Not yet called from computeLinearizedPolynomial: prove.go.diff still builds the
+// polynomial on the host and commits it with commitCanonical.
+func (d *kzgDevice) linearize(n int, polys [quotientPolys][]fr.Element, qcp, pi2 [][]fr.Element,
+	bl, br, bo, bz, h, hRand []fr.Element, alpha, beta, gamma, zeta fr.Element) ([]fr.Element, kzg.Digest,
+	[]fr.Element, error) {
+	if n < 8 || n+3 > d.nCanon || len(qcp) != len(pi2) || len(bl) != 2 || len(br) != 2 || len(bo) != 2 ||
+		len(bz) != 3 || len(h) != 4*n || (hRand != nil && len(hRand) != 2) {
+		return nil, kzg.Digest{}, nil, errLinearizeShape
+	}
+	var devs []*gm.DevicePoly
+	defer func() {
+		for _, dp := range devs {
+			dp.Free()
+		}
+	}()
+	upload := func(p []fr.Element, size int) (*gm.DevicePoly, error) {
+		if len(p) != size {
+			return nil, errLinearizeShape
+		}
+		dp, err := gm.UploadPoly(unsafe.Pointer(&p[0]), size)
+		if err == nil {
+			devs = append(devs, dp)
+		}
+		return dp, err
+	}
+	var fixed [quotientPolys]*gm.DevicePoly
+	var err error
+	for i := range polys {
+		if fixed[i], err = upload(polys[i], n); err != nil {
+			return nil, kzg.Digest{}, nil, err
+		}
+	}
+	in := gm.LinearizeInput{
+		N:  n,
+		Ql: fixed[qQl], Qr: fixed[qQr], Qm: fixed[qQm], Qo: fixed[qQo], Qk: fixed[qQk],
+		S1: fixed[qS1], S2: fixed[qS2], S3: fixed[qS3],
+		L: fixed[qL], R: fixed[qR], O: fixed[qO], Z: fixed[qZ],
+		Bl: unsafe.Pointer(&bl[0]), Br: unsafe.Pointer(&br[0]), Bo: unsafe.Pointer(&bo[0]), Bz: unsafe.Pointer(&bz[0]),
+		Alpha: unsafe.Pointer(&alpha), Beta: unsafe.Pointer(&beta), Gamma: unsafe.Pointer(&gamma),
+		Zeta: unsafe.Pointer(&zeta),
+	}
+	if hRand != nil {
+		in.HRand = unsafe.Pointer(&hRand[0])
+	}
+	for i := range qcp {
+		var a, b *gm.DevicePoly
+		if a, err = upload(qcp[i], n); err != nil {
+			return nil, kzg.Digest{}, nil, err
+		}
+		if b, err = upload(pi2[i], n); err != nil {
+			return nil, kzg.Digest{}, nil, err
+		}
+		in.Qcp, in.Pi2 = append(in.Qcp, a), append(in.Pi2, b)
+	}
+	if in.H, err = upload(h, 4*n); err != nil {
+		return nil, kzg.Digest{}, nil, err
+	}
+	lin, err := gm.AllocPoly(n + 3)
+	if err != nil {
+		return nil, kzg.Digest{}, nil, err
+	}
+	devs = append(devs, lin)
+	evals := make([]fr.Element, 6+len(qcp))
+	out := gm.LinearizeOutput{Lin: lin, Evals: unsafe.Pointer(&evals[0])}
+	if err = gm.PlonkLinearize(gm.BLS12_377, &in, &out); err != nil {
+		return nil, kzg.Digest{}, nil, err
+	}
+	var digest curve.G1Affine
+	if err = d.canonical.CommitResident(lin, 0, n+3, unsafe.Pointer(&digest)); err != nil {
+		return nil, kzg.Digest{}, nil, err
+	}
+	res := make([]fr.Element, n+3)
+	if err = lin.Download(unsafe.Pointer(&res[0]), 0, n+3); err != nil {
+		return nil, kzg.Digest{}, nil, err
+	}
+	return res, digest, evals, nil
 }
 
 // plainForm: a Lagrange or Canonical (not coset) polynomial of |dom|

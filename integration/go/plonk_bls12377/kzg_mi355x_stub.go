@@ -47,6 +47,13 @@ func (d *kzgDevice) ratioZ(int, []fr.Element, []fr.Element, []fr.Element, []fr.E
 	return nil, nil, kzg.Digest{}, errNoGPU
 }
 
+// Not yet called from computeLinearizedPolynomial (prove.go.diff), as in the icicle build.
+func (d *kzgDevice) linearize(int, [quotientPolys][]fr.Element, [][]fr.Element, [][]fr.Element,
+	[]fr.Element, []fr.Element, []fr.Element, []fr.Element, []fr.Element, []fr.Element,
+	fr.Element, fr.Element, fr.Element, fr.Element) ([]fr.Element, kzg.Digest, []fr.Element, error) {
+	return nil, kzg.Digest{}, nil, errNoGPU
+}
+
 func (d *kzgDevice) toCanonical(*iop.Polynomial, *fft.Domain) bool { return false }
 func (d *kzgDevice) toLagrange(*iop.Polynomial, *fft.Domain) bool  { return false }
 
