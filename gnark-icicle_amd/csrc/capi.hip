@@ -14,6 +14,8 @@
 #include "plonk.hpp"
 #include "plonk_lin.hpp"
 #include "plonk_perm.hpp"
+#include "plonk_pk.hpp"
+#include "plonk_session.hpp"
 #include "msm.hpp"
 #include "ntt.hpp"
 #include "runtime.hpp"
@@ -168,6 +170,7 @@ int gm_destroy(gm_ctx* ctx) {
   orphan_pending_msms(ctx);
   // stages parked with keys of this context (their keys may outlive it)
   while (!ctx->spare_keys.empty()) stage_spare_release(ctx->spare_keys.back());
+  while (!ctx->plonk_spare_keys.empty()) plonk_spare_release(ctx->plonk_spare_keys.back());
   for (auto& pr : ctx->pending_reads) hipEventDestroy(pr.second);
   ctx->pending_reads.clear();
   ntt_domains_free(ctx);
@@ -227,6 +230,7 @@ int gm_trim(gm_ctx* ctx) {
   ctx->in_abc = nullptr;
   ctx->in_abc_cap = 0;
   while (!ctx->spare_keys.empty()) stage_spare_release(ctx->spare_keys.back());  // parked stages
+  while (!ctx->plonk_spare_keys.empty()) plonk_spare_release(ctx->plonk_spare_keys.back());  // session buffers
   for (int i = 0; i < gm_ctx::H2D_SLOTS; i++) {
     if (ctx->h2d_pin[i]) hipHostFree(ctx->h2d_pin[i]);
     ctx->h2d_pin[i] = nullptr;
@@ -451,10 +455,9 @@ int msm_wait_t(gm_msm_pending* p, void* out_jac, void* out_aff) {
 }
 }  // namespace
 
-extern "C" {
-
-int gm_msm_async(gm_ctx* ctx, int curve, int g2, const void* scalars_dev, const void* points_dev, size_t n,
-                 gm_msm_pending** out) {
+// gm_msm_async, also over a prepared point set (msm.hpp)
+int gm::msm_async_queue(gm_ctx* ctx, int curve, int g2, const void* scalars_dev, const void* points_dev, size_t n,
+                        bool prepared, gm_msm_pending** out) {
   if (!ctx || !out) return GM_ERR_INVALID;
   if (int rc = check_curve(curve)) return rc;
   // no CtxLock: nothing is queued on ctx->stream here (gm_ctx::pending_reads)
@@ -519,11 +522,11 @@ int gm_msm_async(gm_ctx* ctx, int curve, int g2, const void* scalars_dev, const 
       const void* sc = scalars_dev;
       const void* pt = points_dev;
       if (curve == GM_BN254)
-        rc = g2 ? msm_device_launch<CurveBN254, true>(ctx, a, sc, pt, n, false, nullptr, p->tail, inputs_read)
-                : msm_device_launch<CurveBN254, false>(ctx, a, sc, pt, n, false, nullptr, p->tail, inputs_read);
+        rc = g2 ? msm_device_launch<CurveBN254, true>(ctx, a, sc, pt, n, prepared, nullptr, p->tail, inputs_read)
+                : msm_device_launch<CurveBN254, false>(ctx, a, sc, pt, n, prepared, nullptr, p->tail, inputs_read);
       else
-        rc = g2 ? msm_device_launch<CurveBLS12377, true>(ctx, a, sc, pt, n, false, nullptr, p->tail, inputs_read)
-                : msm_device_launch<CurveBLS12377, false>(ctx, a, sc, pt, n, false, nullptr, p->tail, inputs_read);
+        rc = g2 ? msm_device_launch<CurveBLS12377, true>(ctx, a, sc, pt, n, prepared, nullptr, p->tail, inputs_read)
+                : msm_device_launch<CurveBLS12377, false>(ctx, a, sc, pt, n, prepared, nullptr, p->tail, inputs_read);
     }
   }
   if (inputs_read && rc) hipEventDestroy(inputs_read);
@@ -536,6 +539,13 @@ int gm_msm_async(gm_ctx* ctx, int curve, int g2, const void* scalars_dev, const 
   ctx->live_msms.push_back(p);
   *out = p;
   return GM_OK;
+}
+
+extern "C" {
+
+int gm_msm_async(gm_ctx* ctx, int curve, int g2, const void* scalars_dev, const void* points_dev, size_t n,
+                 gm_msm_pending** out) {
+  return gm::msm_async_queue(ctx, curve, g2, scalars_dev, points_dev, n, false, out);
 }
 
 int gm_msm_wait(gm_msm_pending* p, void* out_jac, void* out_affine) {
@@ -910,6 +920,84 @@ int gm_plonk_linearize(gm_ctx* ctx, int curve, const gm_plonk_linearize_in* in, 
   GM_HIP(hipStreamSynchronize(ctx->stream));
   prof_collect(ctx);
   return rc;
+}
+
+// ---- PLONK proving key resident on the device (plonk_pk.hip) ------------------------
+static int refuse_null(const char* what) {
+  set_error(std::string(what) + ": a required pointer is NULL");
+  return GM_ERR_INVALID;
+}
+
+int gm_plonk_pk_upload(gm_ctx* ctx, int curve, const gm_plonk_pk_host* pk, unsigned flags, gm_plonk_pk** out) {
+  if (!ctx || !pk || !out) return refuse_null("plonk pk upload");
+  if (int rc = check_curve(curve)) return rc;
+  return plonk_pk_upload(ctx, curve, pk, flags, out);
+}
+
+int gm_plonk_pk_bytes(const gm_plonk_pk* pk, size_t* resident_bytes, size_t* coset_cache_bytes) {
+  if (!pk) return refuse_null("plonk pk bytes");
+  if (resident_bytes) *resident_bytes = pk->resident_bytes;
+  if (coset_cache_bytes) *coset_cache_bytes = pk->cache_bytes;
+  return GM_OK;
+}
+
+int gm_plonk_pk_free(gm_ctx* ctx, gm_plonk_pk* pk) {
+  if (!ctx || !pk) return refuse_null("plonk pk free");
+  if (pk->ctx != ctx) {
+    set_error("plonk pk free: the key was uploaded on another context");
+    return GM_ERR_INVALID;
+  }
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  GM_HIP(hipStreamSynchronize(ctx->stream));
+  plonk_pk_release(pk);
+  return GM_OK;
+}
+
+// ---- PLONK prover session: the five rounds on a resident key (plonk_session.hip) ----
+int gm_plonk_session_begin(gm_ctx* ctx, gm_plonk_pk* pk, gm_plonk_session** out) {
+  if (!ctx || !pk || !out) return refuse_null("plonk session begin");
+  return plonk_session_begin(ctx, pk, out);
+}
+
+int gm_plonk_session_bsb22(gm_plonk_session* s, size_t j, const void* committed_host, void* digest_affine) {
+  if (!s) return refuse_null("plonk session bsb22");
+  return plonk_session_bsb22(s, j, committed_host, digest_affine);
+}
+
+int gm_plonk_session_round1(gm_plonk_session* s, const gm_plonk_round1_in* in, void* lro_affine) {
+  if (!s || !in) return refuse_null("plonk session round 1");
+  return plonk_session_round1(s, in, lro_affine);
+}
+
+int gm_plonk_session_round2(gm_plonk_session* s, const void* beta, const void* gamma, void* z_affine) {
+  if (!s) return refuse_null("plonk session round 2");
+  return plonk_session_round2(s, beta, gamma, z_affine);
+}
+
+int gm_plonk_session_round3(gm_plonk_session* s, const void* alpha, void* h_affine) {
+  if (!s) return refuse_null("plonk session round 3");
+  return plonk_session_round3(s, alpha, h_affine);
+}
+
+int gm_plonk_session_round4(gm_plonk_session* s, const void* zeta, void* lin_affine, void* claimed,
+                            void* z_shifted_value, void* z_shifted_h_affine) {
+  if (!s) return refuse_null("plonk session round 4");
+  return plonk_session_round4(s, zeta, lin_affine, claimed, z_shifted_value, z_shifted_h_affine);
+}
+
+int gm_plonk_session_round5(gm_plonk_session* s, const void* kzg_gamma, void* batch_h_affine) {
+  if (!s) return refuse_null("plonk session round 5");
+  return plonk_session_round5(s, kzg_gamma, batch_h_affine);
+}
+
+int gm_plonk_session_free(gm_plonk_session* s) {
+  if (!s) return refuse_null("plonk session free");
+  gm::CtxLock g(s->ctx);
+  GM_HIP(hipSetDevice(s->ctx->device));
+  GM_HIP(hipStreamSynchronize(s->ctx->stream));
+  plonk_session_release(s);
+  return GM_OK;
 }
 
 // ---- NTT --------------------------------------------------------------------------

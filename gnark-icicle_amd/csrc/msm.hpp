@@ -7,6 +7,7 @@
 #include "curves.hpp"
 
 struct gm_ctx;
+struct gm_msm_pending;
 
 namespace gm {
 struct Arena;
@@ -175,4 +176,8 @@ template <class C, bool G2>
 int msm_precompute_points(gm_ctx* ctx, const void* gnark_points, size_t n, const MsmPrecomp& pre, void* dst);
 template <class C, bool G2>
 size_t msm_internal_point_bytes();
+// gm_msm_async (include/gnark_mi355x.h) with the choice of the point layout:
+// prepared = a prepared set (gm_points_upload), not gnark-layout points.  Finished by gm_msm_wait.
+int msm_async_queue(gm_ctx* ctx, int curve, int g2, const void* scalars_dev, const void* points_dev, size_t n,
+                    bool prepared, gm_msm_pending** out);
 }  // namespace gm

@@ -43,6 +43,10 @@ namespace gm {
 constexpr int PLONK_TPB = 256;
 // workspace slots (n elements each); the BSB22 pairs follow
 enum { PQ_QL, PQ_QR, PQ_QM, PQ_QO, PQ_QK, PQ_S1, PQ_S2, PQ_S3, PQ_L, PQ_R, PQ_O, PQ_Z, PQ_L1, PQ_FIXED };
+// With a key's coset cache (PlonkCosetCache, plonk.hpp) only the per-proof
+// polynomials go through workspace; the PI2_j follow.  The fixed ones are read
+// from the cache's block of the coset, slots PC_* (plonk.hpp), the Qcp_j last.
+enum { PW_QK, PW_L, PW_R, PW_O, PW_Z, PW_FIXED };
 
 // the constants of one coset, by value
 template <class P>
@@ -66,13 +70,39 @@ GM_DEV uint32_t pq_brev(uint32_t x, int bits) { return __brev(x) >> (32 - bits);
 // ev: the (PQ_FIXED + 2 nb) coset evaluations, slot k at element k n; out: the
 // coset's block of the 4n vector.  Lane p reads element p of every slot (32 B,
 // consecutive lanes consecutive) and one element of the Z slot elsewhere.
-template <class P>
-__global__ void __launch_bounds__(PLONK_TPB) k_plonk_constraint(const void* __restrict__ ev, size_t n, int logn,
+// CACHED: ev holds the PW_FIXED + nb per-proof slots only and fx, the key's cache
+// block of this coset, the PC_FIXED + nb fixed ones.  Which of the two holds slot
+// k, and where, is a table of compile-time constants (PQ_WHERE), so either
+// variant does the address arithmetic the kernel did before.
+struct PqWhere {
+  bool fixed;
+  int slot;
+};
+__device__ constexpr PqWhere PQ_WHERE[PQ_FIXED] = {
+    {true, PC_QL}, {true, PC_QR}, {true, PC_QM}, {true, PC_QO}, {false, PW_QK}, {true, PC_S1}, {true, PC_S2},
+    {true, PC_S3}, {false, PW_L}, {false, PW_R}, {false, PW_O}, {false, PW_Z},  {true, PC_L1}};
+
+template <class P, bool CACHED>
+__global__ void __launch_bounds__(PLONK_TPB) k_plonk_constraint(const void* __restrict__ ev,
+                                                                const void* __restrict__ fx, size_t n, int logn,
                                                                 int nb, const Fe<P>* __restrict__ wbrev,
                                                                 QuotCoset<P> q, void* __restrict__ out) {
   const size_t p = (size_t)blockIdx.x * PLONK_TPB + threadIdx.x;
   if (p >= n) return;
-  auto at = [&](int k, size_t idx) { return fe_load_g<P>(ev, (size_t)k * n + idx); };
+  // one of the thirteen named slots
+  auto at = [&](int k, size_t idx) {
+    if (!CACHED) return fe_load_g<P>(ev, (size_t)k * n + idx);
+    return PQ_WHERE[k].fixed ? fe_load_g<P>(fx, (size_t)PQ_WHERE[k].slot * n + idx)
+                             : fe_load_g<P>(ev, (size_t)PQ_WHERE[k].slot * n + idx);
+  };
+  // the BSB22 pairs behind them
+  auto qcp_at = [&](int j, size_t idx) {
+    return CACHED ? fe_load_g<P>(fx, (size_t)(PC_FIXED + j) * n + idx)
+                  : fe_load_g<P>(ev, (size_t)(PQ_FIXED + j) * n + idx);
+  };
+  auto pi2_at = [&](int j, size_t idx) {
+    return fe_load_g<P>(ev, (size_t)((CACHED ? PW_FIXED : PQ_FIXED + nb) + j) * n + idx);
+  };
   auto U = [](const FeG<P>& g) { return fe_unpack<P>(g); };
   // Z(w0 x): evaluation index brev(p) + 1 mod n
   const size_t pn = pq_brev((pq_brev((uint32_t)p, logn) + 1) & (uint32_t)(n - 1), logn);
@@ -94,7 +124,7 @@ __global__ void __launch_bounds__(PLONK_TPB) k_plonk_constraint(const void* __re
   Fe<P> acc = fe_mul(gate, U(q.k_gate));
   if (nb) {
     Fe<P> bsb = fe_zero<P>();  // gnark times 2^(256 - 29 N)
-    for (int k = 0; k < nb; k++) bsb = fe_add(bsb, fe_mul(at(PQ_FIXED + k, p), at(PQ_FIXED + nb + k, p)));
+    for (int k = 0; k < nb; k++) bsb = fe_add(bsb, fe_mul(qcp_at(k, p), pi2_at(k, p)));
     acc = fe_add(acc, fe_mul(bsb, U(q.k_bsb)));
   }
   // permutation
@@ -129,8 +159,34 @@ static FeG<Fr> gnark_words(const HF& h) {
   return r;
 }
 
+// The cache of a key: the fixed polynomials' values on the four cosets, exactly
+// what the loop below leaves in their workspace slots (same calls, same order of
+// operations), block i = coset i, slot k of a block at element (i slots + k) n.
 template <class C>
-int plonk_quotient_device(gm_ctx* ctx, const gm_plonk_quotient_in* in, void* h_dev) {
+int plonk_coset_cache_build(gm_ctx* ctx, size_t n, const void* const* fixed, size_t nb, void* cache) {
+  using Fr = typename C::Fr;
+  using HF = host::F<typename C::HFr>;
+  const size_t slots = PC_FIXED + nb;
+  const FeG<Fr> ninv = gnark_words<HF, Fr>(host::finv(host::from_u64<typename C::HFr>(n)));
+  int rc;
+  for (int i = 0; i < 4; i++)
+    for (size_t k = 0; k < slots; k++) {
+      char* slot = (char*)cache + 32 * n * (i * slots + k);
+      const size_t f = k < PC_L1 ? k : k - 1;  // fixed[]: ql qr qm qo s1 s2 s3 qcp_0 ..
+      if (k == PC_L1) {
+        hipLaunchKernelGGL(k_fill_const<Fr>, dim3(blocks_for(n, PLONK_TPB)), dim3(PLONK_TPB), 0, ctx->stream,
+                           (void*)slot, n, ninv);
+        GM_HIP(hipGetLastError());
+      } else {
+        GM_HIP(hipMemcpyAsync(slot, fixed[f], 32 * n, hipMemcpyDeviceToDevice, ctx->stream));
+      }
+      if ((rc = coset4_ntt_device<C>(ctx, slot, n, i))) return rc;
+    }
+  return GM_OK;
+}
+
+template <class C>
+int plonk_quotient_device(gm_ctx* ctx, const gm_plonk_quotient_in* in, void* h_dev, const PlonkCosetCache* cache) {
   using Fr = typename C::Fr;
   using HFr = typename C::HFr;
   using HF = host::F<HFr>;
@@ -192,9 +248,22 @@ int plonk_quotient_device(gm_ctx* ctx, const gm_plonk_quotient_in* in, void* h_d
   w0 = w0 * w0;
   const uint64_t en[1] = {n};
 
+  if (cache && (!cache->base || cache->n != n || cache->nb_bsb != nb)) {
+    set_error("plonk quotient: the coset cache belongs to another key shape");
+    return GM_ERR_INVALID;
+  }
+  // workspace slot of source k: its own, or with a cache only the per-proof ones
+  std::vector<int> ws(src.size());
+  size_t nws = 0;
+  for (size_t k = 0; k < src.size(); k++) {
+    const bool per_proof = k == PQ_QK || (k >= PQ_L && k <= PQ_Z) || k >= PQ_FIXED + nb;
+    ws[k] = !cache ? (int)k : per_proof ? (int)nws : -1;
+    nws += per_proof;
+  }
+  if (!cache) nws = src.size();
   Arena arena(ctx);
   DevBuf ev;
-  if ((rc = ev.alloc(arena, 32 * n * src.size()))) return rc;
+  if ((rc = ev.alloc(arena, 32 * n * nws))) return rc;
   const void* wbrev;
   if ((rc = ntt_brev_roots<C>(ctx, n, &wbrev))) return rc;
   const FeG<Fr> ninv = gnark_words<HF, Fr>(host::finv(host::from_u64<HFr>(n)));
@@ -204,7 +273,8 @@ int plonk_quotient_device(gm_ctx* ctx, const gm_plonk_quotient_in* in, void* h_d
 
   for (int i = 0; i < 4; i++) {
     for (size_t k = 0; k < src.size(); k++) {
-      char* slot = ev.as<char>() + 32 * n * k;
+      if (ws[k] < 0) continue;  // in the key's cache
+      char* slot = ev.as<char>() + 32 * n * ws[k];
       if (k == PQ_L1) {
         hipLaunchKernelGGL(k_fill_const<Fr>, dim3(grid), dim3(PLONK_TPB), 0, ctx->stream, (void*)slot, n, ninv);
         GM_HIP(hipGetLastError());
@@ -239,14 +309,25 @@ int plonk_quotient_device(gm_ctx* ctx, const gm_plonk_quotient_in* in, void* h_d
     q.k_lag = I(alpha * alpha * zhinv * kin);
     const size_t block = (size_t)(((i & 1) << 1) | (i >> 1)) * n;  // brev2(i) n
     ProfScope ps(ctx, "plonk_constraint");
-    hipLaunchKernelGGL(k_plonk_constraint<Fr>, dim3(grid), dim3(PLONK_TPB), 0, ctx->stream, (const void*)ev.p, n,
-                       logn, (int)nb, (const Fe<Fr>*)wbrev, q, (void*)((char*)h_dev + 32 * block));
+    if (cache) {
+      const void* fx = (const char*)cache->base + 32 * n * (PC_FIXED + nb) * i;
+      hipLaunchKernelGGL((k_plonk_constraint<Fr, true>), dim3(grid), dim3(PLONK_TPB), 0, ctx->stream,
+                         (const void*)ev.p, fx, n, logn, (int)nb, (const Fe<Fr>*)wbrev, q,
+                         (void*)((char*)h_dev + 32 * block));
+    } else {
+      hipLaunchKernelGGL((k_plonk_constraint<Fr, false>), dim3(grid), dim3(PLONK_TPB), 0, ctx->stream,
+                         (const void*)ev.p, (const void*)nullptr, n, logn, (int)nb, (const Fe<Fr>*)wbrev, q,
+                         (void*)((char*)h_dev + 32 * block));
+    }
     GM_HIP(hipGetLastError());
   }
   return ntt_device<C>(ctx, h_dev, 4 * n, true, true, true);
 }
 
-template int plonk_quotient_device<CurveBN254>(gm_ctx*, const gm_plonk_quotient_in*, void*);
-template int plonk_quotient_device<CurveBLS12377>(gm_ctx*, const gm_plonk_quotient_in*, void*);
+template int plonk_quotient_device<CurveBN254>(gm_ctx*, const gm_plonk_quotient_in*, void*, const PlonkCosetCache*);
+template int plonk_quotient_device<CurveBLS12377>(gm_ctx*, const gm_plonk_quotient_in*, void*,
+                                                  const PlonkCosetCache*);
+template int plonk_coset_cache_build<CurveBN254>(gm_ctx*, size_t, const void* const*, size_t, void*);
+template int plonk_coset_cache_build<CurveBLS12377>(gm_ctx*, size_t, const void* const*, size_t, void*);
 
 }  // namespace gm

@@ -1,0 +1,169 @@
+// A PLONK proving key resident on the device -- what gnark's plonk.ProvingKey
+// (backend/plonk/bls12-377/setup.go) holds for the prover, uploaded once:
+//   * both KZG SRSs in the MSM's internal layout (gm_points_upload's form);
+//   * the fixed polynomials in canonical form (quotient, linearization, batch
+//     opening), by the reversal plus inverse transform gm_plonk_perm_z uses for Z;
+//     s1, s2, s3 and the incomplete Qk also as the Lagrange values they arrive in
+//     (gm_plonk_perm_z takes the former that way; the session completes the latter);
+//   * unless GM_PLONK_PK_NO_COSET_CACHE, the values of ql, qr, qm, qo, s1, s2, s3,
+//     L1 and every qcp_j on the four cosets of the 4n domain, as the quotient's
+//     transforms leave them (plonk_coset_cache_build, plonk.hip): 32 of the 52
+//     transforms of a quotient at nb_bsb = 0 are then done once per key.
+// No host pointer is kept.
+#include <cstring>
+
+#include "curves.hpp"
+#include "msm.hpp"
+#include "ntt.hpp"
+#include "plonk_pk.hpp"
+#include "runtime.hpp"
+
+namespace gm {
+
+void plonk_spare_release(gm_plonk_pk* pk) {
+  if (pk->ctx) {
+    auto& v = pk->ctx->plonk_spare_keys;
+    v.erase(std::remove(v.begin(), v.end(), pk), v.end());
+  }
+  if (pk->spare_buf) hipFree(pk->spare_buf);
+  pk->spare_buf = nullptr;
+  pk->spare_bytes = 0;
+}
+
+void plonk_pk_release(gm_plonk_pk* pk) {
+  if (!pk) return;
+  if (pk->ctx) hipSetDevice(pk->ctx->device);
+  plonk_spare_release(pk);
+  for (void* p : {pk->srs_canonical, pk->srs_lagrange, pk->polys, pk->cache})
+    if (p) hipFree(p);
+  delete pk;
+}
+
+namespace {
+
+int alloc_dev(void** out, size_t bytes, const char* what) {
+  const hipError_t e = hipMalloc(out, bytes);
+  if (e != hipSuccess) {
+    *out = nullptr;
+    set_error(std::string("plonk pk: hipMalloc of the ") + what + " (" + std::to_string(bytes) +
+              " bytes): " + hipGetErrorString(e));
+    return GM_ERR_OOM;
+  }
+  return GM_OK;
+}
+
+template <class C>
+int upload_t(gm_ctx* ctx, const gm_plonk_pk_host* h, unsigned flags, gm_plonk_pk* pk) {
+  const size_t n = h->n, nb = h->nb_bsb;
+  int rc;
+  if ((rc = gm_points_upload(ctx, pk->curve, 0, h->srs_canonical, h->srs_canonical_len, &pk->srs_canonical)))
+    return rc;
+  if ((rc = gm_points_upload(ctx, pk->curve, 0, h->srs_lagrange, n, &pk->srs_lagrange))) return rc;
+  const size_t pb = 2 * fp_bytes(pk->curve);
+  pk->edge.resize(6 * pb);
+  for (int k = 0; k < 3; k++) {
+    memcpy(&pk->edge[k * pb], (const char*)h->srs_canonical + k * pb, pb);
+    memcpy(&pk->edge[(3 + k) * pb], (const char*)h->srs_canonical + (n + k) * pb, pb);
+  }
+
+  const size_t poly_bytes = 32 * n * (gm_plonk_pk::NCANON + nb + 4);
+  if ((rc = alloc_dev(&pk->polys, poly_bytes, "polynomials"))) return rc;
+  Arena arena(ctx);
+  DevBuf tmp;
+  if ((rc = tmp.alloc(arena, 32 * n))) return rc;
+  // Lagrange regular (at `lag`, or from the host through tmp) -> canonical regular at dst
+  auto canonical = [&](const void* host, void* lag, void* dst) -> int {
+    void* src = lag ? lag : tmp.p;
+    GM_HIP(hipMemcpyAsync(src, host, 32 * n, hipMemcpyHostToDevice, ctx->stream));
+    if (int r = bitrev_copy_device<C>(ctx, dst, src, n)) return r;
+    return ntt_device<C>(ctx, dst, n, true, true, false);
+  };
+  auto can = [&](size_t k) { return const_cast<void*>(pk->canonical(k)); };
+  auto lag = [&](size_t k) { return const_cast<void*>(pk->lagrange(k)); };
+  const void* sel[4] = {h->ql, h->qr, h->qm, h->qo};
+  for (int k = 0; k < 4; k++)
+    if ((rc = canonical(sel[k], nullptr, can(gm_plonk_pk::QL + k)))) return rc;
+  const void* perm[3] = {h->s1, h->s2, h->s3};
+  for (int k = 0; k < 3; k++)
+    if ((rc = canonical(perm[k], lag(gm_plonk_pk::LAG_S1 + k), can(gm_plonk_pk::S1 + k)))) return rc;
+  for (size_t j = 0; j < nb; j++)
+    if ((rc = canonical(h->qcp[j], nullptr, can(gm_plonk_pk::NCANON + j)))) return rc;
+  GM_HIP(hipMemcpyAsync(lag(gm_plonk_pk::LAG_QK), h->qk, 32 * n, hipMemcpyHostToDevice, ctx->stream));
+  pk->resident_bytes = poly_bytes + msm_internal_point_bytes<C, false>() * (h->srs_canonical_len + n);
+
+  if (!(flags & GM_PLONK_PK_NO_COSET_CACHE)) {
+    const size_t cb = 4 * (PC_FIXED + nb) * n * 32;
+    if ((rc = alloc_dev(&pk->cache, cb, "coset cache"))) return rc;
+    std::vector<const void*> fixed;
+    for (size_t k = 0; k < gm_plonk_pk::NCANON + nb; k++) fixed.push_back(pk->canonical(k));
+    if ((rc = plonk_coset_cache_build<C>(ctx, n, fixed.data(), nb, pk->cache))) return rc;
+    pk->cache_bytes = cb;
+    pk->resident_bytes += cb;
+  }
+  GM_HIP(hipStreamSynchronize(ctx->stream));
+  return GM_OK;
+}
+
+}  // namespace
+
+int plonk_pk_upload(gm_ctx* ctx, int curve, const gm_plonk_pk_host* h, unsigned flags, gm_plonk_pk** out) {
+  const size_t n = h->n, nb = h->nb_bsb;
+  int logn = 0;
+  while (((size_t)1 << logn) < n && logn < 62) logn++;
+  const int adicity = curve == GM_BN254 ? CurveBN254::TWO_ADICITY : CurveBLS12377::TWO_ADICITY;
+  if (((size_t)1 << logn) != n || n < 8 || logn + 2 > adicity || logn + 2 > 30) {
+    set_error("plonk pk: n must be a power of two >= 8 with 4n within the 2-adicity");
+    return GM_ERR_INVALID;
+  }
+  if (flags & ~GM_PLONK_PK_NO_COSET_CACHE) {
+    set_error("plonk pk: unknown flag");
+    return GM_ERR_INVALID;
+  }
+  for (const void* p : {h->ql, h->qr, h->qm, h->qo, h->qk, h->s1, h->s2, h->s3, h->srs_canonical, h->srs_lagrange})
+    if (!p) {
+      set_error("plonk pk: the polynomials and both SRSs must be non-null");
+      return GM_ERR_INVALID;
+    }
+  if (h->srs_canonical_len < n + 3) {
+    set_error("plonk pk: the canonical SRS needs at least n + 3 points");
+    return GM_ERR_INVALID;
+  }
+  if (h->nb_public > n) {
+    set_error("plonk pk: more public inputs than rows");
+    return GM_ERR_INVALID;
+  }
+  if (nb > 1024 || (nb && (!h->qcp || !h->commitment_row))) {
+    set_error("plonk pk: nb_bsb > 0 needs the qcp table and the commitment rows (at most 1024 gates)");
+    return GM_ERR_INVALID;
+  }
+  for (size_t j = 0; j < nb; j++) {
+    if (!h->qcp[j]) {
+      set_error("plonk pk: a qcp entry is null");
+      return GM_ERR_INVALID;
+    }
+    if (h->commitment_row[j] >= n) {
+      set_error("plonk pk: a commitment row lies outside the domain");
+      return GM_ERR_INVALID;
+    }
+  }
+  CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  gm_plonk_pk* pk = new gm_plonk_pk;
+  pk->ctx = ctx;
+  pk->curve = curve;
+  pk->n = n;
+  pk->nb_public = h->nb_public;
+  pk->nb_bsb = nb;
+  if (nb) pk->commitment_row.assign(h->commitment_row, h->commitment_row + nb);
+  pk->srs_canonical_len = h->srs_canonical_len;
+  int rc = curve == GM_BN254 ? upload_t<CurveBN254>(ctx, h, flags, pk) : upload_t<CurveBLS12377>(ctx, h, flags, pk);
+  if (rc) {
+    hipStreamSynchronize(ctx->stream);  // nothing queued may outlive the buffers
+    plonk_pk_release(pk);
+    return rc;
+  }
+  *out = pk;
+  return GM_OK;
+}
+
+}  // namespace gm

@@ -137,6 +137,9 @@ struct gm_ctx {
   // keys holding a parked stage of this context (gm_g16_stage_free): gm_trim
   // releases those stages' buffers
   std::vector<gm_g16_pk*> spare_keys;
+  // PLONK keys holding the buffer of a freed session of this context
+  // (gm_plonk_session_free): gm_trim releases those buffers
+  std::vector<gm_plonk_pk*> plonk_spare_keys;
 };
 
 namespace gm {

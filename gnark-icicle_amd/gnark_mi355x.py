@@ -55,6 +55,9 @@ SYMBOLS = [
     "gm_g16_stage_begin", "gm_g16_stage_put_range", "gm_g16_stage_put_indexed", "gm_g16_stage_prove",
     "gm_g16_stage_free", "gm_msm_async", "gm_msm_wait", "gm_r1cs_upload", "gm_r1cs_free", "gm_r1cs_eval",
     "gm_g16_prove_r1cs", "gm_g16_stage_prove_r1cs",
+    "gm_plonk_pk_upload", "gm_plonk_pk_bytes", "gm_plonk_pk_free", "gm_plonk_session_begin",
+    "gm_plonk_session_bsb22", "gm_plonk_session_round1", "gm_plonk_session_round2", "gm_plonk_session_round3",
+    "gm_plonk_session_round4", "gm_plonk_session_round5", "gm_plonk_session_free",
 ]
 # test-only library (include/gnark_mi355x_testhooks.h, libgnark_mi355x_testhooks.so)
 TEST_SYMBOLS = ["gm_test_field_op", "gm_test_point_op", "gm_test_stage_replay_chain"]
@@ -106,6 +109,27 @@ class _PlonkLinearizeIn(ctypes.Structure):
 class _PlonkLinearizeOut(ctypes.Structure):
     """gm_plonk_linearize_out (include/gnark_mi355x.h)."""
     _fields_ = [(k, ctypes.c_void_p) for k in ("lin",) + PLONK_LIN_BLINDED + ("evals",)]
+
+
+PLONK_PK_POLYS = ("ql", "qr", "qm", "qo", "qk", "s1", "s2", "s3")
+PLONK_PK_NO_COSET_CACHE = 1
+
+
+class _PlonkPkHost(ctypes.Structure):
+    """gm_plonk_pk_host (include/gnark_mi355x.h)."""
+    _fields_ = ([("n", ctypes.c_size_t), ("nb_public", ctypes.c_size_t)]
+                + [(k, ctypes.c_void_p) for k in PLONK_PK_POLYS]
+                + [("nb_bsb", ctypes.c_size_t), ("qcp", ctypes.POINTER(ctypes.c_void_p)),
+                   ("commitment_row", ctypes.POINTER(ctypes.c_size_t)), ("srs_canonical", ctypes.c_void_p),
+                   ("srs_canonical_len", ctypes.c_size_t), ("srs_lagrange", ctypes.c_void_p)])
+
+
+PLONK_ROUND1_FIELDS = ("l", "r", "o", "public_inputs", "commitment_vals", "bl", "br", "bo", "bz", "h_rand")
+
+
+class _PlonkRound1In(ctypes.Structure):
+    """gm_plonk_round1_in (include/gnark_mi355x.h)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in PLONK_ROUND1_FIELDS]
 
 
 _lib = None
@@ -224,6 +248,17 @@ def load_library(path: str = LIB_PATH):
     L.gm_g16_stage_prove_r1cs.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.gm_msm_async.argtypes = [vp, i, i, vp, vp, sz, pvp]
     L.gm_msm_wait.argtypes = [vp, vp, vp]
+    L.gm_plonk_pk_upload.argtypes = [vp, i, ctypes.POINTER(_PlonkPkHost), ctypes.c_uint, pvp]
+    L.gm_plonk_pk_bytes.argtypes = [vp, psz, psz]
+    L.gm_plonk_pk_free.argtypes = [vp, vp]
+    L.gm_plonk_session_begin.argtypes = [vp, vp, pvp]
+    L.gm_plonk_session_bsb22.argtypes = [vp, sz, vp, vp]
+    L.gm_plonk_session_round1.argtypes = [vp, ctypes.POINTER(_PlonkRound1In), vp]
+    L.gm_plonk_session_round2.argtypes = [vp, vp, vp, vp]
+    L.gm_plonk_session_round3.argtypes = [vp, vp, vp]
+    L.gm_plonk_session_round4.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.gm_plonk_session_round5.argtypes = [vp, vp, vp]
+    L.gm_plonk_session_free.argtypes = [vp]
     _lib = L
     return L
 
@@ -1022,6 +1057,132 @@ class Stage:
     def free(self):
         if self.handle:
             load_library().gm_g16_stage_free(self.handle)
+            self.handle = None
+
+
+class PlonkProvingKey:
+    """A PLONK proving key resident on the device (gm_plonk_pk_upload).  polys:
+    host bytes keyed by PLONK_PK_POLYS (n elements each, Lagrange regular; qk
+    without public inputs and commitment values); qcp: list of host bytes;
+    commitment_row: their rows of Qk; srs_canonical / srs_lagrange: gnark G1Affine
+    bytes.  cache=False uploads with GM_PLONK_PK_NO_COSET_CACHE.  A None among
+    the inputs passes a NULL pointer; srs_canonical_len overrides the length
+    taken from the bytes."""
+
+    def __init__(self, ctx: Context, curve, n: int, nb_public: int, polys: dict, qcp, commitment_row,
+                 srs_canonical, srs_lagrange, cache: bool = True, srs_canonical_len: int | None = None):
+        self.ctx, self.curve, self.n, self.nb_public = ctx, curve, n, nb_public
+        self.nb_bsb = len(qcp) if qcp is not None else len(commitment_row or [])
+        h = _PlonkPkHost()
+        h.n, h.nb_public, h.nb_bsb = n, nb_public, self.nb_bsb
+        keep = []
+
+        def ptr(b):
+            if b is None:
+                return None
+            keep.append(_buf(b))
+            return keep[-1].ctypes.data
+
+        for k in PLONK_PK_POLYS:
+            setattr(h, k, ptr(polys[k]))
+        if qcp is not None and self.nb_bsb:
+            tab = (ctypes.c_void_p * self.nb_bsb)(*[ptr(b) for b in qcp])
+            keep.append(tab)
+            h.qcp = ctypes.cast(tab, ctypes.POINTER(ctypes.c_void_p))
+        if commitment_row is not None and self.nb_bsb:
+            rows = (ctypes.c_size_t * self.nb_bsb)(*commitment_row)
+            keep.append(rows)
+            h.commitment_row = ctypes.cast(rows, ctypes.POINTER(ctypes.c_size_t))
+        h.srs_canonical, h.srs_lagrange = ptr(srs_canonical), ptr(srs_lagrange)
+        pb = point_bytes(curve, False)
+        h.srs_canonical_len = (len(srs_canonical) // pb if srs_canonical is not None else 0) \
+            if srs_canonical_len is None else srs_canonical_len
+        out = ctypes.c_void_p()
+        _check(load_library().gm_plonk_pk_upload(ctx.handle, curve_id(curve), ctypes.byref(h),
+                                                 0 if cache else PLONK_PK_NO_COSET_CACHE, ctypes.byref(out)))
+        self.handle = out
+
+    def resident_bytes(self) -> tuple[int, int]:
+        """(resident bytes, coset cache bytes) of gm_plonk_pk_bytes."""
+        a, b = ctypes.c_size_t(), ctypes.c_size_t()
+        _check(load_library().gm_plonk_pk_bytes(self.handle, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def session(self) -> "PlonkSession":
+        return PlonkSession(self)
+
+    def free(self):
+        if self.handle:
+            _check(load_library().gm_plonk_pk_free(self.ctx.handle, self.handle))
+            self.handle = None
+
+
+class PlonkSession:
+    """One proof on a PlonkProvingKey (gm_plonk_session_*): bsb22 per commitment,
+    then round1 .. round5 with the caller's challenges between them.  Challenges
+    and scalars are Montgomery fr.Element bytes, digests gnark G1Affine bytes."""
+
+    def __init__(self, pk: PlonkProvingKey):
+        self.pk = pk
+        h = ctypes.c_void_p()
+        _check(load_library().gm_plonk_session_begin(pk.ctx.handle, pk.handle, ctypes.byref(h)))
+        self.handle = h
+
+    def _pt(self, k: int = 1) -> np.ndarray:
+        return np.zeros(k * point_bytes(self.pk.curve, False), np.uint8)
+
+    @staticmethod
+    def _split(a: np.ndarray, k: int) -> list:
+        b = a.tobytes()
+        w = len(b) // k
+        return [b[w * j:w * (j + 1)] for j in range(k)]
+
+    def bsb22(self, j: int, committed) -> bytes:
+        c = _buf(committed) if committed is not None else None
+        d = self._pt()
+        _check(load_library().gm_plonk_session_bsb22(self.handle, j, _p(c) if c is not None else None, _p(d)))
+        return d.tobytes()
+
+    def round1(self, l, r, o, public_inputs, blinds: dict, commitment_vals=None, h_rand=None) -> list:
+        """[commit(l~), commit(r~), commit(o~)]; blinds keyed bl, br, bo, bz."""
+        a = _PlonkRound1In()
+        vals = dict(blinds, l=l, r=r, o=o, public_inputs=public_inputs, commitment_vals=commitment_vals,
+                    h_rand=h_rand)
+        keep = {k: _buf(v) for k, v in vals.items() if v is not None and len(v)}
+        for k, v in keep.items():
+            setattr(a, k, v.ctypes.data)
+        d = self._pt(3)
+        _check(load_library().gm_plonk_session_round1(self.handle, ctypes.byref(a), _p(d)))
+        return self._split(d, 3)
+
+    def round2(self, beta: bytes, gamma: bytes) -> bytes:
+        b, g, d = _buf(beta), _buf(gamma), self._pt()
+        _check(load_library().gm_plonk_session_round2(self.handle, _p(b), _p(g), _p(d)))
+        return d.tobytes()
+
+    def round3(self, alpha: bytes) -> list:
+        a, d = _buf(alpha), self._pt(3)
+        _check(load_library().gm_plonk_session_round3(self.handle, _p(a), _p(d)))
+        return self._split(d, 3)
+
+    def round4(self, zeta: bytes):
+        """(commit(lin), claimed values [lin, l~, r~, o~, s1, s2, qcp_j at zeta],
+        z~(w zeta), proof of its opening)."""
+        z, lin, hz = _buf(zeta), self._pt(), self._pt()
+        k = 6 + self.pk.nb_bsb
+        claimed = np.zeros(FR_BYTES * k, np.uint8)
+        zs = np.zeros(FR_BYTES, np.uint8)
+        _check(load_library().gm_plonk_session_round4(self.handle, _p(z), _p(lin), _p(claimed), _p(zs), _p(hz)))
+        return lin.tobytes(), self._split(claimed, k), zs.tobytes(), hz.tobytes()
+
+    def round5(self, kzg_gamma: bytes) -> bytes:
+        g, d = _buf(kzg_gamma), self._pt()
+        _check(load_library().gm_plonk_session_round5(self.handle, _p(g), _p(d)))
+        return d.tobytes()
+
+    def free(self):
+        if self.handle:
+            _check(load_library().gm_plonk_session_free(self.handle))
             self.handle = None
 
 

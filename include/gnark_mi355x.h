@@ -56,7 +56,8 @@ int gm_synchronize(gm_ctx* ctx);
  * workspace arenas, the a / b / c input buffer of host-input proves (3 n Fr,
  * 1.5 GB at 2^24), the pinned H2D ring, the cached NTT domain tables and the
  * staging buffers parked with keys by gm_g16_stage_free (3 n + nb_wires Fr plus
- * 64 MiB pinned and 64 MiB device per key).  All
+ * 64 MiB pinned and 64 MiB device per key) and the session buffers parked with
+ * PLONK keys by gm_plonk_session_free.  All
  * are re-created on demand by the next call that needs them.  Refused
  * (GM_ERR_INVALID) while gm_msm_async MSMs are pending.  Call it before
  * uploading a key whose GM_PK_PRECOMPUTE_AUTO decision should see that memory
@@ -352,6 +353,125 @@ typedef struct {
 
 int gm_plonk_linearize(gm_ctx* ctx, int curve, const gm_plonk_linearize_in* in,
                        const gm_plonk_linearize_out* out);
+
+/* ---- PLONK proving key resident on the device (gnark plonk.ProvingKey,
+ *      backend/plonk/bls12-377/setup.go; the PLONK twin of gm_g16_pk_upload) ---------
+ * Uploaded once per circuit; any number of prover sessions run on it one after
+ * another, and none of them writes to it.  Every host polynomial is n Montgomery
+ * fr.Elements, Lagrange basis, regular order (element i is the value at w^i), as
+ * gnark's trace holds them at setup: ql, qr, qm, qo, s1, s2, s3, the qcp_j, and qk
+ * WITHOUT the public inputs and commitment values, which a session writes per
+ * proof to rows [0, nb_public) and commitment_row[j] (prove.go:363-389; the rows
+ * are already offset by nb_public).  srs_canonical is pk.Kzg.G1 (tau^i G,
+ * srs_canonical_len >= n + 3 gnark G1Affine), srs_lagrange is pk.KzgLagrange.G1
+ * (L_i(tau) G, n points).  No host pointer is kept after the call returns.
+ *
+ * The key keeps on the device: both SRSs in the MSM's layout (the form
+ * gm_points_upload makes); every fixed polynomial in the canonical basis, s1, s2,
+ * s3 and qk also as Lagrange values; and, unless GM_PLONK_PK_NO_COSET_CACHE is
+ * set, the values of ql, qr, qm, qo, s1, s2, s3, L1 = (X^n - 1) / (n (X - 1)) and
+ * every qcp_j on each of the four cosets g w1^i <w0> of the 4n domain (gm_plonk_quotient's
+ * names), in the order and number form the quotient's own transforms produce:
+ * 4 (8 + nb_bsb) n elements of 32 bytes (4.3 GB at n = 2^22, nb_bsb = 0).  A
+ * session's quotient then transforms only qk, l, r, o, z and the pi2_j per coset
+ * (5 + nb_bsb transforms instead of 13 + 2 nb_bsb); its results are the same
+ * bytes with and without the cache.  Qk is never cached: it differs per proof.
+ *
+ * gm_plonk_pk_bytes reports the device bytes of the key, the cache included, and
+ * the cache's share (0 without it); either pointer may be NULL.
+ *
+ * GM_ERR_INVALID: NULL context, struct or out (checked before any device call), a
+ * NULL polynomial or SRS, n not a power of two or n < 8 (as gm_plonk_quotient),
+ * srs_canonical_len < n + 3, nb_public > n, nb_bsb > 0 with a NULL table or
+ * entry, nb_bsb > 1024, a commitment_row >= n, an unknown flag. */
+typedef struct gm_plonk_pk gm_plonk_pk;
+typedef struct {
+  size_t n;                 /* domain0 size: power of two, >= 8 */
+  size_t nb_public;         /* rows [0, nb_public) of Qk receive the public inputs */
+  const void *ql, *qr, *qm, *qo, *qk, *s1, *s2, *s3;  /* host, n Fr each, Lagrange regular */
+  size_t nb_bsb;
+  const void* const* qcp;          /* host array of nb_bsb host pointers, n Fr each */
+  const size_t* commitment_row;    /* nb_bsb rows of Qk that receive commitment_vals[j] */
+  const void* srs_canonical;       /* gnark G1Affine */
+  size_t srs_canonical_len;        /* >= n + 3 */
+  const void* srs_lagrange;        /* gnark G1Affine, n points */
+} gm_plonk_pk_host;
+#define GM_PLONK_PK_NO_COSET_CACHE 1u
+int gm_plonk_pk_upload(gm_ctx* ctx, int curve, const gm_plonk_pk_host* pk, unsigned flags, gm_plonk_pk** out);
+int gm_plonk_pk_bytes(const gm_plonk_pk* pk, size_t* resident_bytes, size_t* coset_cache_bytes);
+int gm_plonk_pk_free(gm_ctx* ctx, gm_plonk_pk* pk);
+
+/* ---- PLONK prover session (backend/plonk/bls12-377/prove.go Prove: the five
+ *      rounds on a resident key) ---------------------------------------------------
+ * One session is one proof.  Its buffers live on the device from gm_plonk_session_begin
+ * to gm_plonk_session_free; per proof only the solver's L, R, O, the public inputs,
+ * the blinding scalars and the challenges go in, and digests, claimed values and
+ * opening proofs come out.  The Fiat-Shamir transcript stays with the caller
+ * (ChallengeHash and KZGFoldingHash are prover options): every challenge enters
+ * as one Montgomery fr.Element in host memory, as with gm_kzg_batch_open.  Every
+ * host vector is Montgomery fr.Elements; every digest is one gnark G1Affine.  The
+ * outputs are the bytes prove.go produces for the same inputs.
+ *
+ *  - bsb22 (prove.go:292-327), once per j < nb_bsb before round 1: the committed-
+ *    values polynomial j (n elements, Lagrange regular) is uploaded and kept in
+ *    both bases; digest_affine = its commit over the Lagrange SRS (not blinded).
+ *  - round 1 (:331-417, :458-468, :1114-1127): l, r, o (n elements each, Lagrange
+ *    regular: solution.L / R / O) are uploaded and also taken to canonical form;
+ *    Qk is completed (the key's qk with public_inputs on rows [0, nb_public) and
+ *    commitment_vals[j] on commitment_row[j]); lro_affine receives the three
+ *    commits of the blinded wires P~ = P + (X^n - 1) b: the commit of the values
+ *    over the Lagrange SRS plus sum_k b_k (G_n+k - G_k) over the canonical one.
+ *    bl, br, bo (2 elements: b_0 + b_1 X), bz (3) and h_rand (2, or NULL: no
+ *    StatisticalZK) are copied for the later rounds.
+ *  - round 2 (:565-597): Z as gm_plonk_perm_z defines it, from beta and gamma;
+ *    z_affine = the commit of Z~ = Z + (X^n - 1) bz.
+ *  - round 3 (:486-563, :619-654, :1154-1173): h as gm_plonk_quotient defines it,
+ *    from alpha, read from the key's coset cache where the key has one.  With
+ *    m = n + 2, h_affine receives the commits of h[0:m], h[m:2m], h[2m:3m] over
+ *    the canonical SRS; with h_rand = (rho0, rho1) those of h1 || rho0, of h2
+ *    with [0] -= rho0 followed by rho1, and of h3 with [0] -= rho1.
+ *  - round 4 (:600-617, :656-724): the linearized polynomial as gm_plonk_linearize
+ *    defines it, from zeta; lin_affine = its commit; claimed receives, in the
+ *    order of polysToOpen (:736-744), lin(zeta), l~(zeta), r~(zeta), o~(zeta),
+ *    s1(zeta), s2(zeta), qcp_j(zeta) (6 + nb_bsb elements): what the caller derives
+ *    the folding challenge from; z_shifted_value = z~(w zeta) and
+ *    z_shifted_h_affine = the proof of kzg.Open of Z~ at w zeta.
+ *  - round 5 (:726-767): batch_h_affine = the proof of kzg.BatchOpenSinglePoint of
+ *    [lin, l~, r~, o~, s1, s2, qcp_j] at zeta with the folding challenge kzg_gamma.
+ *
+ * The rounds are a state machine: GM_ERR_INVALID, with a message and the session
+ * left as it was, for a round out of order, a bsb22 call after round 1 or with
+ * j >= nb_bsb, round 1 before every bsb22 call, a NULL required pointer
+ * (public_inputs may be NULL iff nb_public == 0; commitment_vals is NULL iff
+ * nb_bsb == 0), a key of another context.  A NULL context, key, session, input
+ * struct or out is refused before any device call.  Calls on the session's
+ * context are serialised as for every entry; scratch comes from the context's
+ * workspace (gm_trim releases it, also between rounds).  The session must be
+ * freed before its key and its context.  gm_plonk_session_free leaves the
+ * session's device buffer (about 18 + 2 nb_bsb polynomials of n elements) with
+ * the key, and the next gm_plonk_session_begin on that key takes it: a prover
+ * loop allocates once, not per proof, and no proof reads what an earlier one
+ * wrote.  gm_trim, gm_destroy and gm_plonk_pk_free release that buffer;
+ * gm_plonk_pk_bytes does not count it. */
+typedef struct gm_plonk_session gm_plonk_session;
+int gm_plonk_session_begin(gm_ctx* ctx, gm_plonk_pk* pk, gm_plonk_session** out);
+int gm_plonk_session_bsb22(gm_plonk_session* s, size_t j, const void* committed_host, void* digest_affine);
+typedef struct {
+  const void *l, *r, *o;        /* host, n Fr each: solution.L / R / O, Lagrange regular */
+  const void *public_inputs;    /* host, nb_public Fr */
+  const void *commitment_vals;  /* host, nb_bsb Fr (NULL iff nb_bsb == 0) */
+  const void *bl, *br, *bo;     /* host, 2 Fr each */
+  const void *bz;               /* host, 3 Fr */
+  const void *h_rand;           /* host, 2 Fr (StatisticalZK) or NULL */
+} gm_plonk_round1_in;
+int gm_plonk_session_round1(gm_plonk_session* s, const gm_plonk_round1_in* in, void* lro_affine /* 3 points */);
+int gm_plonk_session_round2(gm_plonk_session* s, const void* beta, const void* gamma, void* z_affine);
+int gm_plonk_session_round3(gm_plonk_session* s, const void* alpha, void* h_affine /* 3 points */);
+int gm_plonk_session_round4(gm_plonk_session* s, const void* zeta, void* lin_affine,
+                            void* claimed /* 6 + nb_bsb Fr */, void* z_shifted_value /* 1 Fr */,
+                            void* z_shifted_h_affine);
+int gm_plonk_session_round5(gm_plonk_session* s, const void* kzg_gamma, void* batch_h_affine);
+int gm_plonk_session_free(gm_plonk_session* s);
 
 /* ---- NTT (iciclegnark GenerateTwiddleFactors icicle.go:68,73;
  *      INttOnDevice :489,502; NttOnDevice :490; PolyOps :500;
