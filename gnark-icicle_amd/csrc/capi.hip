@@ -16,6 +16,7 @@
 #include "plonk_perm.hpp"
 #include "plonk_pk.hpp"
 #include "plonk_session.hpp"
+#include "plonk_wires.hpp"
 #include "msm.hpp"
 #include "ntt.hpp"
 #include "runtime.hpp"
@@ -171,6 +172,7 @@ int gm_destroy(gm_ctx* ctx) {
   // stages parked with keys of this context (their keys may outlive it)
   while (!ctx->spare_keys.empty()) stage_spare_release(ctx->spare_keys.back());
   while (!ctx->plonk_spare_keys.empty()) plonk_spare_release(ctx->plonk_spare_keys.back());
+  while (!ctx->plonk_wires.empty()) plonk_wires_release(ctx->plonk_wires.back());  // wire tables not freed
   for (auto& pr : ctx->pending_reads) hipEventDestroy(pr.second);
   ctx->pending_reads.clear();
   ntt_domains_free(ctx);
@@ -998,6 +1000,77 @@ int gm_plonk_session_free(gm_plonk_session* s) {
   GM_HIP(hipStreamSynchronize(s->ctx->stream));
   plonk_session_release(s);
   return GM_OK;
+}
+
+// ---- PLONK session from the witness: resident wire tables (plonk_wires.hip) ----------
+int gm_plonk_wires_upload(gm_ctx* ctx, size_t n, size_t nb_wires, const uint32_t* xa, const uint32_t* xb,
+                          const uint32_t* xc, gm_plonk_wires** out) {
+  if (!ctx || !xa || !xb || !xc || !out) return refuse_null("plonk wires upload");
+  return plonk_wires_upload(ctx, n, nb_wires, xa, xb, xc, out);
+}
+
+int gm_plonk_wires_bytes(const gm_plonk_wires* w, size_t* resident_bytes) {
+  if (!w || !resident_bytes) return refuse_null("plonk wires bytes");
+  *resident_bytes = 3 * w->n * sizeof(uint32_t);
+  return GM_OK;
+}
+
+int gm_plonk_wires_free(gm_ctx* ctx, gm_plonk_wires* w) {
+  if (!ctx || !w) return refuse_null("plonk wires free");
+  if (w->ctx != ctx) {
+    set_error("plonk wires free: the tables were uploaded on another context");
+    return GM_ERR_INVALID;
+  }
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  GM_HIP(hipStreamSynchronize(ctx->stream));
+  plonk_wires_release(w);
+  return GM_OK;
+}
+
+int gm_plonk_gather_lro(gm_ctx* ctx, const gm_plonk_wires* w, const void* witness, void* l, void* r, void* o) {
+  if (!ctx || !w || !witness || !l || !r || !o) return refuse_null("plonk gather lro");
+  if (w->ctx != ctx) {
+    set_error("plonk gather lro: the tables were uploaded on another context");
+    return GM_ERR_INVALID;
+  }
+  // the kernel moves 16-byte halves; [witness), [l), [r), [o) pairwise disjoint
+  const uintptr_t base[4] = {(uintptr_t)witness, (uintptr_t)l, (uintptr_t)r, (uintptr_t)o};
+  const size_t len[4] = {32 * w->nb_wires, 32 * w->n, 32 * w->n, 32 * w->n};
+  for (int a = 0; a < 4; a++) {
+    if (base[a] % 16) {
+      set_error("plonk gather lro: the buffers must be 16-byte aligned");
+      return GM_ERR_INVALID;
+    }
+    for (int b = a + 1; b < 4; b++)
+      if (base[a] < base[b] + len[b] && base[b] < base[a] + len[a]) {
+        set_error(a == 0 ? "plonk gather lro: an output overlaps the witness"
+                         : "plonk gather lro: two outputs overlap");
+        return GM_ERR_INVALID;
+      }
+  }
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  int rc;
+  {
+    ProfScope ps(ctx, "plonk_gather_lro_call");
+    rc = plonk_gather_lro_device(ctx, w, witness, l, r, o);
+  }
+  GM_HIP(hipStreamSynchronize(ctx->stream));
+  prof_collect(ctx);
+  return rc;
+}
+
+int gm_plonk_session_round1_witness(gm_plonk_session* s, const gm_plonk_wires* w,
+                                    const gm_plonk_round1_witness_in* in, void* lro_affine) {
+  if (!s || !w || !in) return refuse_null("plonk session round 1 from the witness");
+  return plonk_session_round1_witness(s, w, in, lro_affine);
+}
+
+int gm_plonk_session_bsb22_sparse(gm_plonk_session* s, size_t j, const uint32_t* rows, const void* values,
+                                  size_t count, void* digest_affine) {
+  if (!s) return refuse_null("plonk session bsb22 sparse");
+  return plonk_session_bsb22_sparse(s, j, rows, values, count, digest_affine);
 }
 
 // ---- NTT --------------------------------------------------------------------------

@@ -1,12 +1,14 @@
 // One PLONK proof on a resident key -- the five rounds of gnark's prover
 // (backend/plonk/bls12-377/prove.go) as calls on buffers that stay on the device
-// from one round to the next.  Per proof the solver's L, R, O, the public inputs,
+// from one round to the next.  Per proof the solver's L, R, O and the public
+// inputs (or, with resident wire tables, the witness they are gathered from),
 // the blinding scalars and the challenges go in; digests, claimed values and
 // opening proofs come out.  The Fiat-Shamir transcript is the caller's.
 //
 // The stages are the library's own device functions (plonk_perm_z_device,
 // plonk_quotient_device, plonk_linearize_device, the kzg.hip polynomial work, the
-// MSM): this file holds no kernel.  What it adds is the data flow between them:
+// MSM, the gather and scatter of plonk_wires.hip): this file holds no kernel.
+// What it adds is the data flow between them:
 //   * l, r, o and the BSB22 polynomials are kept in both bases, Qk is completed
 //     from the key's Lagrange Qk and taken to canonical form;
 //   * wires and Z are committed where they lie, as Lagrange values over the
@@ -19,6 +21,7 @@
 //   * round 3 hands the key's coset cache to the quotient.
 // Every digest is a sum of group elements converted to affine once, so its bytes
 // are those of the commit of the edited coefficient list.
+#include <algorithm>
 #include <cstring>
 
 #include "curves.hpp"
@@ -29,6 +32,7 @@
 #include "plonk_lin.hpp"
 #include "plonk_perm.hpp"
 #include "plonk_session.hpp"
+#include "plonk_wires.hpp"
 #include "runtime.hpp"
 
 namespace gm {
@@ -142,13 +146,12 @@ struct StreamDrain {
   }
 };
 
+// the committed values lie in pi2_lag[j]: their canonical form and their digest
 template <class C>
-int bsb22_t(gm_plonk_session* s, size_t j, const void* committed, void* digest) {
+int bsb22_tail(gm_plonk_session* s, size_t j, void* digest) {
   gm_ctx* ctx = s->ctx;
   const gm_plonk_pk* pk = s->pk;
   const size_t n = pk->n;
-  StreamDrain drain{ctx};
-  GM_HIP(hipMemcpyAsync(s->pi2_lag[j], committed, 32 * n, hipMemcpyHostToDevice, ctx->stream));
   int rc;
   if ((rc = canonical_from<C>(ctx, s->pi2[j], s->pi2_lag[j], n))) return rc;
   typename G1<C>::Jac d;
@@ -158,22 +161,45 @@ int bsb22_t(gm_plonk_session* s, size_t j, const void* committed, void* digest) 
 }
 
 template <class C>
-int round1_t(gm_plonk_session* s, const gm_plonk_round1_in* in, void* lro_affine) {
+int bsb22_t(gm_plonk_session* s, size_t j, const void* committed, void* digest) {
+  gm_ctx* ctx = s->ctx;
+  StreamDrain drain{ctx};
+  GM_HIP(hipMemcpyAsync(s->pi2_lag[j], committed, 32 * s->pk->n, hipMemcpyHostToDevice, ctx->stream));
+  return bsb22_tail<C>(s, j, digest);
+}
+
+// the vector by its nonzero rows: zero-filled on the device, then one scatter of
+// the (row, value) pairs (the rows were checked on the host)
+template <class C>
+int bsb22_sparse_t(gm_plonk_session* s, size_t j, const uint32_t* rows, const void* values, size_t count,
+                   void* digest) {
+  gm_ctx* ctx = s->ctx;
+  Arena arena(ctx);  // before the drain (StreamDrain)
+  DevBuf drows, dvals;
+  int rc;
+  if ((rc = dvals.alloc(arena, 32 * count))) return rc;
+  if ((rc = drows.alloc(arena, sizeof(uint32_t) * count))) return rc;
+  StreamDrain drain{ctx};
+  GM_HIP(hipMemsetAsync(s->pi2_lag[j], 0, 32 * s->pk->n, ctx->stream));
+  if (count) {
+    GM_HIP(hipMemcpyAsync(dvals.p, values, 32 * count, hipMemcpyHostToDevice, ctx->stream));
+    GM_HIP(hipMemcpyAsync(drows.p, rows, sizeof(uint32_t) * count, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = plonk_scatter_rows_device(ctx, s->pi2_lag[j], drows.as<uint32_t>(), dvals.p, count))) return rc;
+  }
+  return bsb22_tail<C>(s, j, digest);
+}
+
+// Round 1 once l, r, o lie in their Lagrange buffers and Qk's copy in h carries
+// the public inputs: the commitment values on their rows, the three commits, the
+// canonical forms, the blinding, the scalars kept.  `in` is either input struct
+// (they share these members).
+template <class C, class In>
+int round1_tail(gm_plonk_session* s, const In* in, void* lro_affine) {
   gm_ctx* ctx = s->ctx;
   const gm_plonk_pk* pk = s->pk;
   const size_t n = pk->n, nb = pk->nb_bsb;
-  StreamDrain drain{ctx};
   void* const lag[3] = {s->l_lag, s->r_lag, s->o_lag};
   void* const can[3] = {s->l, s->r, s->o};
-  const void* const host[3] = {in->l, in->r, in->o};
-  for (int i = 0; i < 3; i++)
-    GM_HIP(hipMemcpyAsync(lag[i], host[i], 32 * n, hipMemcpyHostToDevice, ctx->stream));
-  // Qk: the key's Lagrange values, the public inputs on the first rows, the
-  // commitment values on theirs (prove.go:363-389); completed in h, which is free
-  // until round 3
-  GM_HIP(hipMemcpyAsync(s->h, pk->lagrange(gm_plonk_pk::LAG_QK), 32 * n, hipMemcpyDeviceToDevice, ctx->stream));
-  if (pk->nb_public)
-    GM_HIP(hipMemcpyAsync(s->h, in->public_inputs, 32 * pk->nb_public, hipMemcpyHostToDevice, ctx->stream));
   for (size_t j = 0; j < nb; j++)
     GM_HIP(hipMemcpyAsync((char*)s->h + 32 * pk->commitment_row[j], (const char*)in->commitment_vals + 32 * j, 32,
                           hipMemcpyHostToDevice, ctx->stream));
@@ -211,6 +237,47 @@ int round1_t(gm_plonk_session* s, const gm_plonk_round1_in* in, void* lro_affine
   s->has_h_rand = in->h_rand != nullptr;
   if (in->h_rand) memcpy(s->h_rand, in->h_rand, sizeof(s->h_rand));
   return GM_OK;
+}
+
+template <class C>
+int round1_t(gm_plonk_session* s, const gm_plonk_round1_in* in, void* lro_affine) {
+  gm_ctx* ctx = s->ctx;
+  const gm_plonk_pk* pk = s->pk;
+  const size_t n = pk->n;
+  StreamDrain drain{ctx};
+  void* const lag[3] = {s->l_lag, s->r_lag, s->o_lag};
+  const void* const host[3] = {in->l, in->r, in->o};
+  for (int i = 0; i < 3; i++)
+    GM_HIP(hipMemcpyAsync(lag[i], host[i], 32 * n, hipMemcpyHostToDevice, ctx->stream));
+  // Qk: the key's Lagrange values, the public inputs on the first rows, the
+  // commitment values on theirs (prove.go:363-389); completed in h, which is free
+  // until round 3
+  GM_HIP(hipMemcpyAsync(s->h, pk->lagrange(gm_plonk_pk::LAG_QK), 32 * n, hipMemcpyDeviceToDevice, ctx->stream));
+  if (pk->nb_public)
+    GM_HIP(hipMemcpyAsync(s->h, in->public_inputs, 32 * pk->nb_public, hipMemcpyHostToDevice, ctx->stream));
+  return round1_tail<C>(s, in, lro_affine);
+}
+
+// Round 1 from the solver's values: one upload, l, r, o gathered through the
+// resident wire tables, Qk's public rows from the witness' first nb_public
+// elements (solver.values[:nbPublic] is the public witness)
+template <class C>
+int round1_witness_t(gm_plonk_session* s, const gm_plonk_wires* w, const gm_plonk_round1_witness_in* in,
+                     void* lro_affine) {
+  gm_ctx* ctx = s->ctx;
+  const gm_plonk_pk* pk = s->pk;
+  const size_t n = pk->n;
+  Arena arena(ctx);  // before the drain (StreamDrain)
+  DevBuf wit;
+  int rc;
+  if ((rc = wit.alloc(arena, 32 * w->nb_wires))) return rc;
+  StreamDrain drain{ctx};
+  GM_HIP(hipMemcpyAsync(wit.p, in->witness, 32 * w->nb_wires, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = plonk_gather_lro_device(ctx, w, wit.p, s->l_lag, s->r_lag, s->o_lag))) return rc;
+  GM_HIP(hipMemcpyAsync(s->h, pk->lagrange(gm_plonk_pk::LAG_QK), 32 * n, hipMemcpyDeviceToDevice, ctx->stream));
+  if (pk->nb_public)
+    GM_HIP(hipMemcpyAsync(s->h, wit.p, 32 * pk->nb_public, hipMemcpyDeviceToDevice, ctx->stream));
+  return round1_tail<C>(s, in, lro_affine);
 }
 
 template <class C>
@@ -465,6 +532,51 @@ int plonk_session_round1(gm_plonk_session* s, const gm_plonk_round1_in* in, void
   CtxLock g(s->ctx);
   GM_HIP(hipSetDevice(s->ctx->device));
   const int rc = GM_PLONK_DISPATCH(s, round1_t)(s, in, lro_affine);
+  if (!rc) s->state = 1;
+  return rc;
+}
+
+int plonk_session_bsb22_sparse(gm_plonk_session* s, size_t j, const uint32_t* rows, const void* values, size_t count,
+                               void* digest_affine) {
+  if (s->state != 0) return refuse("bsb22 belongs before round 1");
+  const size_t n = s->pk->n;
+  if (j >= s->pk->nb_bsb) return refuse("bsb22: j is not below the key's nb_bsb");
+  if (!digest_affine || (count && (!rows || !values)))
+    return refuse("bsb22 sparse: the rows, the values and the digest must be non-null");
+  if (count > n) return refuse("bsb22 sparse: more rows than the domain has");
+  std::vector<uint32_t> sorted(rows, rows + count);
+  std::sort(sorted.begin(), sorted.end());
+  if (count && sorted.back() >= n) {
+    set_error("plonk session: bsb22 sparse: row " + std::to_string(sorted.back()) + " lies outside the domain");
+    return GM_ERR_INVALID;
+  }
+  const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+  if (dup != sorted.end()) {
+    set_error("plonk session: bsb22 sparse: row " + std::to_string(*dup) + " is given twice");
+    return GM_ERR_INVALID;
+  }
+  CtxLock g(s->ctx);
+  GM_HIP(hipSetDevice(s->ctx->device));
+  const int rc = GM_PLONK_DISPATCH(s, bsb22_sparse_t)(s, j, rows, values, count, digest_affine);
+  if (!rc) s->bsb_done[j] = 1;
+  return rc;
+}
+
+int plonk_session_round1_witness(gm_plonk_session* s, const gm_plonk_wires* w, const gm_plonk_round1_witness_in* in,
+                                 void* lro_affine) {
+  if (s->state != 0) return refuse("round 1 was already run");
+  for (char done : s->bsb_done)
+    if (!done) return refuse("round 1 needs the bsb22 call of every commitment first");
+  if (!in->witness || !in->bl || !in->br || !in->bo || !in->bz || !lro_affine)
+    return refuse("round 1: the witness, the blinding scalars and the output must be non-null");
+  if ((s->pk->nb_bsb != 0) != (in->commitment_vals != nullptr))
+    return refuse("round 1: commitment_vals must be given exactly when the key has commitments");
+  if (w->ctx != s->ctx) return refuse("round 1: the wire tables were uploaded on another context");
+  if (w->n != s->pk->n) return refuse("round 1: the wire tables have another n than the key");
+  if (w->nb_wires < s->pk->nb_public) return refuse("round 1: fewer wires than the key has public inputs");
+  CtxLock g(s->ctx);
+  GM_HIP(hipSetDevice(s->ctx->device));
+  const int rc = GM_PLONK_DISPATCH(s, round1_witness_t)(s, w, in, lro_affine);
   if (!rc) s->state = 1;
   return rc;
 }

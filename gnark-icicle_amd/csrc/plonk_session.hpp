@@ -31,6 +31,10 @@ namespace gm {
 int plonk_session_begin(gm_ctx* ctx, gm_plonk_pk* pk, gm_plonk_session** out);
 int plonk_session_bsb22(gm_plonk_session* s, size_t j, const void* committed_host, void* digest_affine);
 int plonk_session_round1(gm_plonk_session* s, const gm_plonk_round1_in* in, void* lro_affine);
+int plonk_session_bsb22_sparse(gm_plonk_session* s, size_t j, const uint32_t* rows, const void* values, size_t count,
+                               void* digest_affine);
+int plonk_session_round1_witness(gm_plonk_session* s, const gm_plonk_wires* w, const gm_plonk_round1_witness_in* in,
+                                 void* lro_affine);
 int plonk_session_round2(gm_plonk_session* s, const void* beta, const void* gamma, void* z_affine);
 int plonk_session_round3(gm_plonk_session* s, const void* alpha, void* h_affine);
 int plonk_session_round4(gm_plonk_session* s, const void* zeta, void* lin_affine, void* claimed,

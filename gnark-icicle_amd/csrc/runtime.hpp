@@ -140,6 +140,9 @@ struct gm_ctx {
   // PLONK keys holding the buffer of a freed session of this context
   // (gm_plonk_session_free): gm_trim releases those buffers
   std::vector<gm_plonk_pk*> plonk_spare_keys;
+  // PLONK wire tables uploaded on this context (gm_plonk_wires_upload) and not yet
+  // freed: gm_destroy releases them
+  std::vector<gm_plonk_wires*> plonk_wires;
 };
 
 namespace gm {

@@ -58,6 +58,8 @@ SYMBOLS = [
     "gm_plonk_pk_upload", "gm_plonk_pk_bytes", "gm_plonk_pk_free", "gm_plonk_session_begin",
     "gm_plonk_session_bsb22", "gm_plonk_session_round1", "gm_plonk_session_round2", "gm_plonk_session_round3",
     "gm_plonk_session_round4", "gm_plonk_session_round5", "gm_plonk_session_free",
+    "gm_plonk_wires_upload", "gm_plonk_wires_bytes", "gm_plonk_wires_free", "gm_plonk_gather_lro",
+    "gm_plonk_session_round1_witness", "gm_plonk_session_bsb22_sparse",
 ]
 # test-only library (include/gnark_mi355x_testhooks.h, libgnark_mi355x_testhooks.so)
 TEST_SYMBOLS = ["gm_test_field_op", "gm_test_point_op", "gm_test_stage_replay_chain"]
@@ -130,6 +132,14 @@ PLONK_ROUND1_FIELDS = ("l", "r", "o", "public_inputs", "commitment_vals", "bl", 
 class _PlonkRound1In(ctypes.Structure):
     """gm_plonk_round1_in (include/gnark_mi355x.h)."""
     _fields_ = [(k, ctypes.c_void_p) for k in PLONK_ROUND1_FIELDS]
+
+
+PLONK_ROUND1_WITNESS_FIELDS = ("witness", "commitment_vals", "bl", "br", "bo", "bz", "h_rand")
+
+
+class _PlonkRound1WitnessIn(ctypes.Structure):
+    """gm_plonk_round1_witness_in (include/gnark_mi355x.h)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in PLONK_ROUND1_WITNESS_FIELDS]
 
 
 _lib = None
@@ -259,6 +269,12 @@ def load_library(path: str = LIB_PATH):
     L.gm_plonk_session_round4.argtypes = [vp, vp, vp, vp, vp, vp]
     L.gm_plonk_session_round5.argtypes = [vp, vp, vp]
     L.gm_plonk_session_free.argtypes = [vp]
+    L.gm_plonk_wires_upload.argtypes = [vp, sz, sz, vp, vp, vp, pvp]
+    L.gm_plonk_wires_bytes.argtypes = [vp, psz]
+    L.gm_plonk_wires_free.argtypes = [vp, vp]
+    L.gm_plonk_gather_lro.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.gm_plonk_session_round1_witness.argtypes = [vp, vp, ctypes.POINTER(_PlonkRound1WitnessIn), vp]
+    L.gm_plonk_session_bsb22_sparse.argtypes = [vp, sz, vp, vp, sz, vp]
     _lib = L
     return L
 
@@ -1155,6 +1171,31 @@ class PlonkSession:
         _check(load_library().gm_plonk_session_round1(self.handle, ctypes.byref(a), _p(d)))
         return self._split(d, 3)
 
+    def bsb22_sparse(self, j: int, rows, values) -> bytes:
+        """bsb22 of the vector that is values[i] on row rows[i] and zero elsewhere
+        (gm_plonk_session_bsb22_sparse); rows: integers, already offset by nb_public."""
+        rw = np.ascontiguousarray(rows, dtype=np.uint32) if rows is not None else None
+        v = _buf(values) if values is not None else None
+        count = len(rw) if rw is not None else 0
+        d = self._pt()
+        _check(load_library().gm_plonk_session_bsb22_sparse(
+            self.handle, j, _p(rw) if count else None, _p(v) if v is not None and v.size else None, count, _p(d)))
+        return d.tobytes()
+
+    def round1_witness(self, wires: "PlonkWires", witness, blinds: dict, commitment_vals=None, h_rand=None) -> list:
+        """round1 from the solver's values (gm_plonk_session_round1_witness): l, r, o
+        are gathered on the device through `wires`, the public inputs are the
+        witness' first nb_public elements."""
+        a = _PlonkRound1WitnessIn()
+        vals = dict(blinds, witness=witness, commitment_vals=commitment_vals, h_rand=h_rand)
+        keep = {k: _buf(v) for k, v in vals.items() if v is not None and len(v)}
+        for k, v in keep.items():
+            setattr(a, k, v.ctypes.data)
+        d = self._pt(3)
+        _check(load_library().gm_plonk_session_round1_witness(self.handle, wires.handle if wires is not None else None,
+                                                              ctypes.byref(a), _p(d)))
+        return self._split(d, 3)
+
     def round2(self, beta: bytes, gamma: bytes) -> bytes:
         b, g, d = _buf(beta), _buf(gamma), self._pt()
         _check(load_library().gm_plonk_session_round2(self.handle, _p(b), _p(g), _p(d)))
@@ -1183,6 +1224,39 @@ class PlonkSession:
     def free(self):
         if self.handle:
             _check(load_library().gm_plonk_session_free(self.handle))
+            self.handle = None
+
+
+class PlonkWires:
+    """The wire tables of a PLONK circuit resident on the device
+    (gm_plonk_wires_upload): xa, xb, xc are n wire ids each (anything numpy takes
+    as uint32), complete rows as evaluateLROSmallDomain defines them, every id
+    below nb_wires.  A None among them passes a NULL pointer."""
+
+    def __init__(self, ctx: Context, n: int, nb_wires: int, xa, xb, xc):
+        self.ctx, self.n, self.nb_wires = ctx, n, nb_wires
+        tabs = [np.ascontiguousarray(t, dtype=np.uint32) if t is not None else None for t in (xa, xb, xc)]
+        if any(t is not None and t.size != n for t in tabs):
+            raise ValueError("PlonkWires: every table has n ids")
+        out = ctypes.c_void_p()
+        _check(load_library().gm_plonk_wires_upload(ctx.handle, n, nb_wires,
+                                                    *[_p(t) if t is not None else None for t in tabs],
+                                                    ctypes.byref(out)))
+        self.handle = out
+
+    def gather(self, witness: DeviceBuffer, l: DeviceBuffer, r: DeviceBuffer, o: DeviceBuffer):
+        """gm_plonk_gather_lro: l[i] = witness[xa[i]], r[i] = witness[xb[i]],
+        o[i] = witness[xc[i]] on resident buffers of 32-byte elements."""
+        _check(load_library().gm_plonk_gather_lro(self.ctx.handle, self.handle, witness.ptr, l.ptr, r.ptr, o.ptr))
+
+    def resident_bytes(self) -> int:
+        a = ctypes.c_size_t()
+        _check(load_library().gm_plonk_wires_bytes(self.handle, ctypes.byref(a)))
+        return a.value
+
+    def free(self):
+        if self.handle:
+            _check(load_library().gm_plonk_wires_free(self.ctx.handle, self.handle))
             self.handle = None
 
 

@@ -404,9 +404,11 @@ int gm_plonk_pk_free(gm_ctx* ctx, gm_plonk_pk* pk);
 /* ---- PLONK prover session (backend/plonk/bls12-377/prove.go Prove: the five
  *      rounds on a resident key) ---------------------------------------------------
  * One session is one proof.  Its buffers live on the device from gm_plonk_session_begin
- * to gm_plonk_session_free; per proof only the solver's L, R, O, the public inputs,
- * the blinding scalars and the challenges go in, and digests, claimed values and
- * opening proofs come out.  The Fiat-Shamir transcript stays with the caller
+ * to gm_plonk_session_free; per proof only the solver's L, R, O and the public
+ * inputs (or, with resident wire tables, the witness alone: see
+ * gm_plonk_session_round1_witness below), the committed values, the blinding
+ * scalars and the challenges go in, and digests, claimed values and opening
+ * proofs come out.  The Fiat-Shamir transcript stays with the caller
  * (ChallengeHash and KZGFoldingHash are prover options): every challenge enters
  * as one Montgomery fr.Element in host memory, as with gm_kzg_batch_open.  Every
  * host vector is Montgomery fr.Elements; every digest is one gnark G1Affine.  The
@@ -472,6 +474,73 @@ int gm_plonk_session_round4(gm_plonk_session* s, const void* zeta, void* lin_aff
                             void* z_shifted_h_affine);
 int gm_plonk_session_round5(gm_plonk_session* s, const void* kzg_gamma, void* batch_h_affine);
 int gm_plonk_session_free(gm_plonk_session* s);
+
+/* ---- PLONK session from the witness: resident wire tables (gnark
+ *      evaluateLROSmallDomain, constraint/bls12-377/system.go:173-217; the PLONK
+ *      twin of gm_r1cs_upload) ---------------------------------------------------------
+ * solution.L / R / O are a gather of the solver's values through three wire ids
+ * per row that are fixed when the circuit is compiled:
+ *   l[i] = values[xa[i]]   r[i] = values[xb[i]]   o[i] = values[xc[i]]
+ * gm_plonk_wires_upload puts the three tables (n u32 each, 12 n bytes, reported
+ * by gm_plonk_wires_bytes) on the device once per circuit.  The caller supplies
+ * complete rows, the placeholder rows (i, 0, 0) of the public inputs and the
+ * padding rows (0, 0, 0) included: the library gives no row a meaning.  The
+ * tables belong to no curve and to no key: a gm_plonk_pk is never written, and
+ * one table object serves any number of sessions on keys of the same n.  Every id
+ * is checked < nb_wires on the host before the upload, and gm_last_error names
+ * the first offending table and row; the per-proof kernel reads inside the
+ * witness without a check of its own.  No host pointer is kept.  The object is
+ * freed before its context; gm_destroy releases the tables a context still owns.
+ * GM_ERR_INVALID: a NULL argument (checked before any device call), n not a
+ * power of two or n < 8, nb_wires = 0 or nb_wires > 2^32 - 1, an id >= nb_wires,
+ * gm_plonk_wires_free on another context than the upload's.
+ *
+ * gm_plonk_gather_lro is the stage call on resident buffers: l, r, o (n elements
+ * each) from witness (nb_wires elements) in one launch.  Elements are 32-byte
+ * words moved untouched, so the call takes no curve.  GM_ERR_INVALID: a NULL
+ * argument, tables of another context, a pointer that is not 16-byte aligned, an
+ * output that overlaps the witness or another output.
+ *
+ * gm_plonk_session_round1_witness takes round 1's place in the state machine,
+ * with round 1's preconditions: the witness (nb_wires elements, the solver's
+ * values, whose first nb_public are the public inputs) is uploaded once, l, r, o
+ * are gathered from it on the device, Qk's public rows are taken from
+ * witness[0, nb_public), and the rest is round 1's.  Its outputs, and those of
+ * every later round, are the bytes gm_plonk_session_round1 produces from the
+ * host-gathered l, r, o and public_inputs = witness[0, nb_public).  Refused
+ * besides what round 1 refuses: w->n != the key's n, nb_wires < nb_public, tables
+ * of another context, NULL w or in (before the session is read).
+ *
+ * gm_plonk_session_bsb22_sparse is gm_plonk_session_bsb22 for a committed-values
+ * vector given by its nonzero rows (prove.go:300-311: len(Committed) + 2 rows out
+ * of n): the vector is zero-filled on the device and values[i] written to row
+ * rows[i] for i < count; digest and session state are the bytes the dense call
+ * gives for the same vector.  Rows are already offset by nb_public, as
+ * commitment_row is; each must be < n and they must be pairwise distinct (a
+ * duplicate is refused, not resolved); count = 0 is allowed, count > n refused.
+ *
+ * With the two calls the per-proof host input of a session is the witness
+ * (32 nb_wires bytes, against 96 n for l, r, o), count (row, value) pairs per
+ * commitment, the blinding scalars and the challenges. */
+typedef struct gm_plonk_wires gm_plonk_wires;
+int gm_plonk_wires_upload(gm_ctx* ctx, size_t n, size_t nb_wires,
+                          const uint32_t* xa, const uint32_t* xb, const uint32_t* xc, /* host, n each */
+                          gm_plonk_wires** out);
+int gm_plonk_wires_bytes(const gm_plonk_wires* w, size_t* resident_bytes);
+int gm_plonk_wires_free(gm_ctx* ctx, gm_plonk_wires* w);
+int gm_plonk_gather_lro(gm_ctx* ctx, const gm_plonk_wires* w, const void* witness /* device, nb_wires Fr */,
+                        void* l, void* r, void* o /* device, n Fr each */);
+typedef struct {
+  const void *witness;          /* host, nb_wires Fr: the solver's values */
+  const void *commitment_vals;  /* host, nb_bsb Fr (NULL iff nb_bsb == 0) */
+  const void *bl, *br, *bo;     /* host, 2 Fr each */
+  const void *bz;               /* host, 3 Fr */
+  const void *h_rand;           /* host, 2 Fr or NULL */
+} gm_plonk_round1_witness_in;
+int gm_plonk_session_round1_witness(gm_plonk_session* s, const gm_plonk_wires* w,
+                                    const gm_plonk_round1_witness_in* in, void* lro_affine /* 3 points */);
+int gm_plonk_session_bsb22_sparse(gm_plonk_session* s, size_t j, const uint32_t* rows /* host */,
+                                  const void* values /* host, count Fr */, size_t count, void* digest_affine);
 
 /* ---- NTT (iciclegnark GenerateTwiddleFactors icicle.go:68,73;
  *      INttOnDevice :489,502; NttOnDevice :490; PolyOps :500;
