@@ -16,6 +16,7 @@
 #include "plonk_perm.hpp"
 #include "plonk_pk.hpp"
 #include "plonk_session.hpp"
+#include "plonk_setup.hpp"
 #include "plonk_wires.hpp"
 #include "msm.hpp"
 #include "ntt.hpp"
@@ -1071,6 +1072,45 @@ int gm_plonk_session_bsb22_sparse(gm_plonk_session* s, size_t j, const uint32_t*
                                   size_t count, void* digest_affine) {
   if (!s) return refuse_null("plonk session bsb22 sparse");
   return plonk_session_bsb22_sparse(s, j, rows, values, count, digest_affine);
+}
+
+// ---- PLONK setup on the device (plonk_setup.hip) --------------------------------------
+int gm_kzg_srs_lagrange(gm_ctx* ctx, int curve, const void* srs_dev, size_t n, void* lagrange_dev) {
+  if (!ctx || !srs_dev || !lagrange_dev) return refuse_null("kzg srs lagrange");
+  if (int rc = check_curve(curve)) return rc;
+  // in place or disjoint: the last pass writes while other lanes may still read
+  const uintptr_t a = (uintptr_t)srs_dev, b = (uintptr_t)lagrange_dev;
+  const size_t len = 2 * fp_bytes(curve) * n;
+  if (a != b && a < b + len && b < a + len) {
+    set_error("kzg srs lagrange: the output overlaps the input without being the input");
+    return GM_ERR_INVALID;
+  }
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  return curve == GM_BN254 ? kzg_srs_lagrange_device<CurveBN254>(ctx, srs_dev, n, lagrange_dev)
+                           : kzg_srs_lagrange_device<CurveBLS12377>(ctx, srs_dev, n, lagrange_dev);
+}
+
+int gm_plonk_sigma(gm_ctx* ctx, int curve, size_t n, const int64_t* perm_host, void* s1_dev, void* s2_dev,
+                   void* s3_dev) {
+  if (!ctx || !perm_host || !s1_dev || !s2_dev || !s3_dev) return refuse_null("plonk sigma");
+  if (int rc = check_curve(curve)) return rc;
+  if (n == 0 || (n & (n - 1)) || n > (size_t(1) << 30)) {
+    set_error("plonk sigma: n must be a power of two, 2 <= n <= 2^30");
+    return GM_ERR_INVALID;
+  }
+  if (int rc = plonk_perm_check(n, perm_host)) return rc;
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  return curve == GM_BN254 ? plonk_sigma_device<CurveBN254>(ctx, n, perm_host, s1_dev, s2_dev, s3_dev)
+                           : plonk_sigma_device<CurveBLS12377>(ctx, n, perm_host, s1_dev, s2_dev, s3_dev);
+}
+
+int gm_plonk_pk_setup(gm_ctx* ctx, int curve, const gm_plonk_setup_host* in, unsigned flags, gm_plonk_pk** out,
+                      void* vk_digests, void* srs_lagrange_out) {
+  if (!ctx || !in || !out) return refuse_null("plonk pk setup");
+  if (int rc = check_curve(curve)) return rc;
+  return plonk_pk_setup(ctx, curve, in, flags, out, vk_digests, srs_lagrange_out);
 }
 
 // ---- NTT --------------------------------------------------------------------------

@@ -1250,7 +1250,19 @@ int ntt_brev_roots(gm_ctx* ctx, size_t n, const void** tab) {
   return GM_OK;
 }
 
+template <class C>
+int ntt_root(int logn, void* w_host) {
+  if (logn < 0 || logn > C::TWO_ADICITY) {
+    set_error("ntt: the domain size lies outside the 2-adicity");
+    return GM_ERR_INVALID;
+  }
+  const auto w = host_omega<C>(logn);
+  memcpy(w_host, w.v, sizeof(w.v));
+  return GM_OK;
+}
+
 #define GM_NTT_INST(C)                                                                   \
+  template int ntt_root<C>(int, void*);                                                    \
   template int ntt_device<C>(gm_ctx*, void*, size_t, bool, bool, bool);                   \
   template int poly_ops_device<C>(gm_ctx*, void*, const void*, const void*, size_t,        \
                                   const void*);                                           \

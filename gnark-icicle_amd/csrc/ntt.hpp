@@ -43,5 +43,8 @@ int coset4_ntt_device(gm_ctx* ctx, void* v, size_t n, int i);
 // *tab: n internal-form elements w0^brev(p), cached with the domain
 template <class C>
 int ntt_brev_roots(gm_ctx* ctx, size_t n, const void** tab);
+// *w_host = the generator w of the domain of size 2^logn, fft.NewDomain's (one gnark element)
+template <class C>
+int ntt_root(int logn, void* w_host);
 void ntt_domains_free(gm_ctx* ctx);
 }  // namespace gm

@@ -52,44 +52,51 @@ int alloc_dev(void** out, size_t bytes, const char* what) {
   return GM_OK;
 }
 
+// the affine form of an MSM's result, as the session's digests take it
 template <class C>
-int upload_t(gm_ctx* ctx, const gm_plonk_pk_host* h, unsigned flags, gm_plonk_pk* pk) {
-  const size_t n = h->n, nb = h->nb_bsb;
-  int rc;
-  if ((rc = gm_points_upload(ctx, pk->curve, 0, h->srs_canonical, h->srs_canonical_len, &pk->srs_canonical)))
-    return rc;
-  if ((rc = gm_points_upload(ctx, pk->curve, 0, h->srs_lagrange, n, &pk->srs_lagrange))) return rc;
-  const size_t pb = 2 * fp_bytes(pk->curve);
-  pk->edge.resize(6 * pb);
-  for (int k = 0; k < 3; k++) {
-    memcpy(&pk->edge[k * pb], (const char*)h->srs_canonical + k * pb, pb);
-    memcpy(&pk->edge[(3 + k) * pb], (const char*)h->srs_canonical + (n + k) * pb, pb);
-  }
+int commit_affine(gm_ctx* ctx, const void* scalars, const void* srs, size_t m, void* out) {
+  using HP = typename GroupSel<C, false>::HF;
+  HP j[3];
+  if (int rc = msm_device<C, false>(ctx, scalars, srs, m, j, true)) return rc;
+  const host::Aff<HP> a = host::to_aff(host::Jac<HP>{j[0], j[1], j[2]});
+  memcpy(out, &a, sizeof(a));
+  return GM_OK;
+}
 
-  const size_t poly_bytes = 32 * n * (gm_plonk_pk::NCANON + nb + 4);
-  if ((rc = alloc_dev(&pk->polys, poly_bytes, "polynomials"))) return rc;
+template <class C>
+int finish_t(gm_ctx* ctx, const PlonkPkFixed& f, unsigned flags, gm_plonk_pk* pk, void* vk_digests) {
+  const size_t n = f.n, nb = f.nb_bsb;
+  int rc;
+  const size_t pb = 2 * fp_bytes(pk->curve);
   Arena arena(ctx);
   DevBuf tmp;
   if ((rc = tmp.alloc(arena, 32 * n))) return rc;
-  // Lagrange regular (at `lag`, or from the host through tmp) -> canonical regular at dst
-  auto canonical = [&](const void* host, void* lag, void* dst) -> int {
+  // Lagrange regular (at `lag`, or from the host through tmp; host == nullptr: it
+  // lies at `lag` already) -> canonical regular at dst; its digest while it is there
+  auto canonical = [&](const void* host, void* lag, void* dst, size_t digest) -> int {
     void* src = lag ? lag : tmp.p;
-    GM_HIP(hipMemcpyAsync(src, host, 32 * n, hipMemcpyHostToDevice, ctx->stream));
+    if (host) GM_HIP(hipMemcpyAsync(src, host, 32 * n, hipMemcpyHostToDevice, ctx->stream));
     if (int r = bitrev_copy_device<C>(ctx, dst, src, n)) return r;
-    return ntt_device<C>(ctx, dst, n, true, true, false);
+    if (int r = ntt_device<C>(ctx, dst, n, true, true, false)) return r;
+    if (!vk_digests) return GM_OK;
+    return commit_affine<C>(ctx, src, pk->srs_lagrange, n, (char*)vk_digests + pb * digest);
   };
   auto can = [&](size_t k) { return const_cast<void*>(pk->canonical(k)); };
   auto lag = [&](size_t k) { return const_cast<void*>(pk->lagrange(k)); };
-  const void* sel[4] = {h->ql, h->qr, h->qm, h->qo};
+  // the verifying key's order: S1 S2 S3 Ql Qr Qm Qo Qk Qcp_j
+  const void* sel[4] = {f.ql, f.qr, f.qm, f.qo};
   for (int k = 0; k < 4; k++)
-    if ((rc = canonical(sel[k], nullptr, can(gm_plonk_pk::QL + k)))) return rc;
-  const void* perm[3] = {h->s1, h->s2, h->s3};
+    if ((rc = canonical(sel[k], nullptr, can(gm_plonk_pk::QL + k), 3 + k))) return rc;
   for (int k = 0; k < 3; k++)
-    if ((rc = canonical(perm[k], lag(gm_plonk_pk::LAG_S1 + k), can(gm_plonk_pk::S1 + k)))) return rc;
+    if ((rc = canonical(nullptr, lag(gm_plonk_pk::LAG_S1 + k), can(gm_plonk_pk::S1 + k), k))) return rc;
   for (size_t j = 0; j < nb; j++)
-    if ((rc = canonical(h->qcp[j], nullptr, can(gm_plonk_pk::NCANON + j)))) return rc;
-  GM_HIP(hipMemcpyAsync(lag(gm_plonk_pk::LAG_QK), h->qk, 32 * n, hipMemcpyHostToDevice, ctx->stream));
-  pk->resident_bytes = poly_bytes + msm_internal_point_bytes<C, false>() * (h->srs_canonical_len + n);
+    if ((rc = canonical(f.qcp[j], nullptr, can(gm_plonk_pk::NCANON + j), 8 + j))) return rc;
+  GM_HIP(hipMemcpyAsync(lag(gm_plonk_pk::LAG_QK), f.qk, 32 * n, hipMemcpyHostToDevice, ctx->stream));
+  if (vk_digests)
+    if ((rc = commit_affine<C>(ctx, lag(gm_plonk_pk::LAG_QK), pk->srs_lagrange, n, (char*)vk_digests + pb * 7)))
+      return rc;
+  const size_t poly_bytes = 32 * n * (gm_plonk_pk::NCANON + nb + 4);
+  pk->resident_bytes = poly_bytes + msm_internal_point_bytes<C, false>() * (f.srs_canonical_len + n);
 
   if (!(flags & GM_PLONK_PK_NO_COSET_CACHE)) {
     const size_t cb = 4 * (PC_FIXED + nb) * n * 32;
@@ -106,8 +113,8 @@ int upload_t(gm_ctx* ctx, const gm_plonk_pk_host* h, unsigned flags, gm_plonk_pk
 
 }  // namespace
 
-int plonk_pk_upload(gm_ctx* ctx, int curve, const gm_plonk_pk_host* h, unsigned flags, gm_plonk_pk** out) {
-  const size_t n = h->n, nb = h->nb_bsb;
+int plonk_pk_check(int curve, const PlonkPkFixed& f, unsigned flags, bool other_null) {
+  const size_t n = f.n, nb = f.nb_bsb;
   int logn = 0;
   while (((size_t)1 << logn) < n && logn < 62) logn++;
   const int adicity = curve == GM_BN254 ? CurveBN254::TWO_ADICITY : CurveBLS12377::TWO_ADICITY;
@@ -119,44 +126,84 @@ int plonk_pk_upload(gm_ctx* ctx, int curve, const gm_plonk_pk_host* h, unsigned 
     set_error("plonk pk: unknown flag");
     return GM_ERR_INVALID;
   }
-  for (const void* p : {h->ql, h->qr, h->qm, h->qo, h->qk, h->s1, h->s2, h->s3, h->srs_canonical, h->srs_lagrange})
-    if (!p) {
-      set_error("plonk pk: the polynomials and both SRSs must be non-null");
-      return GM_ERR_INVALID;
-    }
-  if (h->srs_canonical_len < n + 3) {
+  for (const void* p : {f.ql, f.qr, f.qm, f.qo, f.qk, f.srs_canonical})
+    if (!p) other_null = true;
+  if (other_null) {
+    set_error("plonk pk: the polynomials and both SRSs must be non-null");
+    return GM_ERR_INVALID;
+  }
+  if (f.srs_canonical_len < n + 3) {
     set_error("plonk pk: the canonical SRS needs at least n + 3 points");
     return GM_ERR_INVALID;
   }
-  if (h->nb_public > n) {
+  if (f.nb_public > n) {
     set_error("plonk pk: more public inputs than rows");
     return GM_ERR_INVALID;
   }
-  if (nb > 1024 || (nb && (!h->qcp || !h->commitment_row))) {
+  if (nb > 1024 || (nb && (!f.qcp || !f.commitment_row))) {
     set_error("plonk pk: nb_bsb > 0 needs the qcp table and the commitment rows (at most 1024 gates)");
     return GM_ERR_INVALID;
   }
   for (size_t j = 0; j < nb; j++) {
-    if (!h->qcp[j]) {
+    if (!f.qcp[j]) {
       set_error("plonk pk: a qcp entry is null");
       return GM_ERR_INVALID;
     }
-    if (h->commitment_row[j] >= n) {
+    if (f.commitment_row[j] >= n) {
       set_error("plonk pk: a commitment row lies outside the domain");
       return GM_ERR_INVALID;
     }
   }
-  CtxLock g(ctx);
-  GM_HIP(hipSetDevice(ctx->device));
+  return GM_OK;
+}
+
+int plonk_pk_begin(gm_ctx* ctx, int curve, const PlonkPkFixed& f, gm_plonk_pk** out) {
+  const size_t n = f.n, nb = f.nb_bsb;
   gm_plonk_pk* pk = new gm_plonk_pk;
+  *out = pk;
   pk->ctx = ctx;
   pk->curve = curve;
   pk->n = n;
-  pk->nb_public = h->nb_public;
+  pk->nb_public = f.nb_public;
   pk->nb_bsb = nb;
-  if (nb) pk->commitment_row.assign(h->commitment_row, h->commitment_row + nb);
-  pk->srs_canonical_len = h->srs_canonical_len;
-  int rc = curve == GM_BN254 ? upload_t<CurveBN254>(ctx, h, flags, pk) : upload_t<CurveBLS12377>(ctx, h, flags, pk);
+  if (nb) pk->commitment_row.assign(f.commitment_row, f.commitment_row + nb);
+  pk->srs_canonical_len = f.srs_canonical_len;
+  if (int rc = gm_points_upload(ctx, curve, 0, f.srs_canonical, f.srs_canonical_len, &pk->srs_canonical)) return rc;
+  const size_t pb = 2 * fp_bytes(curve);
+  pk->edge.resize(6 * pb);
+  for (int k = 0; k < 3; k++) {
+    memcpy(&pk->edge[k * pb], (const char*)f.srs_canonical + k * pb, pb);
+    memcpy(&pk->edge[(3 + k) * pb], (const char*)f.srs_canonical + (n + k) * pb, pb);
+  }
+  return alloc_dev(&pk->polys, 32 * n * (gm_plonk_pk::NCANON + nb + 4), "polynomials");
+}
+
+int plonk_pk_finish(gm_ctx* ctx, const PlonkPkFixed& f, unsigned flags, gm_plonk_pk* pk, void* vk_digests) {
+  return pk->curve == GM_BN254 ? finish_t<CurveBN254>(ctx, f, flags, pk, vk_digests)
+                               : finish_t<CurveBLS12377>(ctx, f, flags, pk, vk_digests);
+}
+
+int plonk_pk_upload(gm_ctx* ctx, int curve, const gm_plonk_pk_host* h, unsigned flags, gm_plonk_pk** out) {
+  const PlonkPkFixed f = {h->n,      h->nb_public, h->ql,  h->qr,  h->qm, h->qo, h->qk,
+                          h->nb_bsb, h->qcp,       h->commitment_row, h->srs_canonical, h->srs_canonical_len};
+  if (int rc = plonk_pk_check(curve, f, flags, !h->s1 || !h->s2 || !h->s3 || !h->srs_lagrange)) return rc;
+  const size_t n = h->n;
+  CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  gm_plonk_pk* pk = nullptr;
+  int rc = plonk_pk_begin(ctx, curve, f, &pk);
+  if (!rc) rc = gm_points_upload(ctx, curve, 0, h->srs_lagrange, n, &pk->srs_lagrange);
+  if (!rc) {
+    // s1, s2, s3 into their Lagrange slots, where gm_plonk_perm_z reads them
+    const void* perm[3] = {h->s1, h->s2, h->s3};
+    for (int k = 0; k < 3 && !rc; k++)
+      if (hipMemcpyAsync(const_cast<void*>(pk->lagrange(gm_plonk_pk::LAG_S1 + k)), perm[k], 32 * n,
+                         hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+        set_error("plonk pk: upload of s1, s2, s3 failed");
+        rc = GM_ERR_DEVICE;
+      }
+  }
+  if (!rc) rc = plonk_pk_finish(ctx, f, flags, pk, nullptr);
   if (rc) {
     hipStreamSynchronize(ctx->stream);  // nothing queued may outlive the buffers
     plonk_pk_release(pk);

@@ -43,8 +43,33 @@ struct gm_plonk_pk {
 };
 
 namespace gm {
+// What both ways of making a key are given (gm_plonk_pk_host and
+// gm_plonk_setup_host share these members): the key's fixed part.
+struct PlonkPkFixed {
+  size_t n, nb_public;
+  const void *ql, *qr, *qm, *qo, *qk;
+  size_t nb_bsb;
+  const void* const* qcp;
+  const size_t* commitment_row;
+  const void* srs_canonical;
+  size_t srs_canonical_len;
+};
 // Every argument is checked on the host before the first device call.
 int plonk_pk_upload(gm_ctx* ctx, int curve, const gm_plonk_pk_host* host, unsigned flags, gm_plonk_pk** out);
+// The three steps of plonk_pk_upload, shared with plonk_pk_setup (plonk_setup.hip):
+//  * the refusals (other_null: a pointer of the caller's own part is NULL);
+//  * a new key with the canonical SRS prepared, the six edge points copied and the
+//    polynomials allocated (the caller holds the context's lock);
+//  * the tail, once pk->srs_lagrange is prepared and s1, s2, s3 lie in their
+//    Lagrange slots: every polynomial in the bases the prover takes it in, the
+//    coset cache.  vk_digests (host, 8 + nb_bsb gnark G1Affine, or NULL) receives
+//    the commits of S1 S2 S3 Ql Qr Qm Qo Qk Qcp_j over the Lagrange SRS, taken
+//    while each polynomial's Lagrange values are on the device.
+// After a failure of the second or third the caller drains the stream and
+// releases the key.
+int plonk_pk_check(int curve, const PlonkPkFixed& f, unsigned flags, bool other_null);
+int plonk_pk_begin(gm_ctx* ctx, int curve, const PlonkPkFixed& f, gm_plonk_pk** out);
+int plonk_pk_finish(gm_ctx* ctx, const PlonkPkFixed& f, unsigned flags, gm_plonk_pk* pk, void* vk_digests);
 void plonk_pk_release(gm_plonk_pk* pk);
 // frees the key's parked session buffer and takes the key off its context's list
 void plonk_spare_release(gm_plonk_pk* pk);

@@ -60,6 +60,7 @@ SYMBOLS = [
     "gm_plonk_session_round4", "gm_plonk_session_round5", "gm_plonk_session_free",
     "gm_plonk_wires_upload", "gm_plonk_wires_bytes", "gm_plonk_wires_free", "gm_plonk_gather_lro",
     "gm_plonk_session_round1_witness", "gm_plonk_session_bsb22_sparse",
+    "gm_kzg_srs_lagrange", "gm_plonk_sigma", "gm_plonk_pk_setup",
 ]
 # test-only library (include/gnark_mi355x_testhooks.h, libgnark_mi355x_testhooks.so)
 TEST_SYMBOLS = ["gm_test_field_op", "gm_test_point_op", "gm_test_stage_replay_chain"]
@@ -124,6 +125,19 @@ class _PlonkPkHost(ctypes.Structure):
                 + [("nb_bsb", ctypes.c_size_t), ("qcp", ctypes.POINTER(ctypes.c_void_p)),
                    ("commitment_row", ctypes.POINTER(ctypes.c_size_t)), ("srs_canonical", ctypes.c_void_p),
                    ("srs_canonical_len", ctypes.c_size_t), ("srs_lagrange", ctypes.c_void_p)])
+
+
+PLONK_SETUP_POLYS = ("ql", "qr", "qm", "qo", "qk")
+
+
+class _PlonkSetupHost(ctypes.Structure):
+    """gm_plonk_setup_host (include/gnark_mi355x.h)."""
+    _fields_ = ([("n", ctypes.c_size_t), ("nb_public", ctypes.c_size_t)]
+                + [(k, ctypes.c_void_p) for k in PLONK_SETUP_POLYS]
+                + [("permutation", ctypes.POINTER(ctypes.c_int64)),
+                   ("nb_bsb", ctypes.c_size_t), ("qcp", ctypes.POINTER(ctypes.c_void_p)),
+                   ("commitment_row", ctypes.POINTER(ctypes.c_size_t)), ("srs_canonical", ctypes.c_void_p),
+                   ("srs_canonical_len", ctypes.c_size_t)])
 
 
 PLONK_ROUND1_FIELDS = ("l", "r", "o", "public_inputs", "commitment_vals", "bl", "br", "bo", "bz", "h_rand")
@@ -275,6 +289,9 @@ def load_library(path: str = LIB_PATH):
     L.gm_plonk_gather_lro.argtypes = [vp, vp, vp, vp, vp, vp]
     L.gm_plonk_session_round1_witness.argtypes = [vp, vp, ctypes.POINTER(_PlonkRound1WitnessIn), vp]
     L.gm_plonk_session_bsb22_sparse.argtypes = [vp, sz, vp, vp, sz, vp]
+    L.gm_kzg_srs_lagrange.argtypes = [vp, i, vp, sz, vp]
+    L.gm_plonk_sigma.argtypes = [vp, i, sz, ctypes.POINTER(ctypes.c_int64), vp, vp, vp]
+    L.gm_plonk_pk_setup.argtypes = [vp, i, ctypes.POINTER(_PlonkSetupHost), ctypes.c_uint, pvp, vp, vp]
     _lib = L
     return L
 
@@ -700,6 +717,31 @@ class Context:
                                                 n, out.ptr))
         return out
 
+    # ---- PLONK setup ----------------------------------------------------------
+    def kzg_srs_lagrange(self, curve, srs: DeviceBuffer, n: int, out: DeviceBuffer | None = None) -> DeviceBuffer:
+        """gm_kzg_srs_lagrange: the Lagrange form of the first n points of srs (gnark
+        G1Affine on the device), into out (srs itself for in place) or a new buffer."""
+        if out is None:
+            out = self.malloc(point_bytes(curve, False) * n)
+        _check(load_library().gm_kzg_srs_lagrange(self.handle, curve_id(curve), srs.ptr, n, out.ptr))
+        return out
+
+    def plonk_sigma(self, curve, n: int, permutation) -> tuple[DeviceBuffer, DeviceBuffer, DeviceBuffer]:
+        """gm_plonk_sigma: s1, s2, s3 (n Montgomery elements each, on the device) from
+        gnark's trace.S, 3n integers (anything numpy takes as int64)."""
+        perm = np.ascontiguousarray(permutation, dtype=np.int64)
+        if perm.size != 3 * n:
+            raise ValueError("the permutation has 3n entries")
+        s = [self.malloc(FR_BYTES * n) for _ in range(3)]
+        try:
+            _check(load_library().gm_plonk_sigma(self.handle, curve_id(curve), n,
+                                                 perm.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                                 s[0].ptr, s[1].ptr, s[2].ptr))
+        except GmError:
+            for b in s:
+                b.free()
+            raise
+        return s[0], s[1], s[2]
 
     # ---- test hooks ---------------------------------------------------------
     def test_field_op(self, curve, kind: int, op: int, a: bytes, b: bytes) -> bytes:
@@ -1117,6 +1159,59 @@ class PlonkProvingKey:
         _check(load_library().gm_plonk_pk_upload(ctx.handle, curve_id(curve), ctypes.byref(h),
                                                  0 if cache else PLONK_PK_NO_COSET_CACHE, ctypes.byref(out)))
         self.handle = out
+
+    @classmethod
+    def setup(cls, ctx: Context, curve, n: int, nb_public: int, polys: dict, permutation, qcp, commitment_row,
+              srs_canonical, cache: bool = True, srs_canonical_len: int | None = None, lagrange: bool = False,
+              digests: bool = True):
+        """The key from what gnark's Setup holds (gm_plonk_pk_setup): polys keyed by
+        PLONK_SETUP_POLYS, permutation = trace.S (3n integers), the canonical SRS
+        alone.  Returns (key, the 8 + nb_bsb digests S1 S2 S3 Ql Qr Qm Qo Qk Qcp_j as
+        gnark G1Affine bytes, the derived Lagrange SRS bytes or None).  A None among
+        the inputs, or digests=False, passes a NULL pointer."""
+        self = cls.__new__(cls)
+        self.ctx, self.curve, self.n, self.nb_public = ctx, curve, n, nb_public
+        self.nb_bsb = len(qcp) if qcp is not None else len(commitment_row or [])
+        self.handle = None
+        h = _PlonkSetupHost()
+        h.n, h.nb_public, h.nb_bsb = n, nb_public, self.nb_bsb
+        keep = []
+
+        def ptr(b):
+            if b is None:
+                return None
+            keep.append(_buf(b))
+            return keep[-1].ctypes.data
+
+        for k in PLONK_SETUP_POLYS:
+            setattr(h, k, ptr(polys[k]))
+        if permutation is not None:
+            perm = np.ascontiguousarray(permutation, dtype=np.int64)
+            if perm.size != 3 * n:
+                raise ValueError("the permutation has 3n entries")
+            keep.append(perm)
+            h.permutation = perm.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        if qcp is not None and self.nb_bsb:
+            tab = (ctypes.c_void_p * self.nb_bsb)(*[ptr(b) for b in qcp])
+            keep.append(tab)
+            h.qcp = ctypes.cast(tab, ctypes.POINTER(ctypes.c_void_p))
+        if commitment_row is not None and self.nb_bsb:
+            rows = (ctypes.c_size_t * self.nb_bsb)(*commitment_row)
+            keep.append(rows)
+            h.commitment_row = ctypes.cast(rows, ctypes.POINTER(ctypes.c_size_t))
+        h.srs_canonical = ptr(srs_canonical)
+        pb = point_bytes(curve, False)
+        h.srs_canonical_len = (len(srs_canonical) // pb if srs_canonical is not None else 0) \
+            if srs_canonical_len is None else srs_canonical_len
+        dig = np.zeros(pb * (8 + self.nb_bsb), np.uint8) if digests else None
+        lag = np.zeros(pb * n, np.uint8) if lagrange else None
+        out = ctypes.c_void_p()
+        _check(load_library().gm_plonk_pk_setup(ctx.handle, curve_id(curve), ctypes.byref(h),
+                                                0 if cache else PLONK_PK_NO_COSET_CACHE, ctypes.byref(out),
+                                                _p(dig) if digests else None, _p(lag) if lagrange else None))
+        self.handle = out
+        db = dig.tobytes() if digests else b""
+        return self, [db[i:i + pb] for i in range(0, len(db), pb)], (lag.tobytes() if lagrange else None)
 
     def resident_bytes(self) -> tuple[int, int]:
         """(resident bytes, coset cache bytes) of gm_plonk_pk_bytes."""

@@ -542,6 +542,59 @@ int gm_plonk_session_round1_witness(gm_plonk_session* s, const gm_plonk_wires* w
 int gm_plonk_session_bsb22_sparse(gm_plonk_session* s, size_t j, const uint32_t* rows /* host */,
                                   const void* values /* host, count Fr */, size_t count, void* digest_affine);
 
+/* ---- PLONK setup on the device (gnark plonk.Setup, backend/plonk/bls12-377/setup.go,
+ *      and the kzg.ToLagrangeG1 its caller runs first, backend/plonk/plonk.go:113-117) --
+ * gm_kzg_srs_lagrange is the Lagrange-form SRS: srs_dev holds n gnark G1Affine
+ * points on the device, the first n of pk.Kzg.G1 ((0,0) = infinity is allowed), and
+ * lagrange_dev receives n gnark G1Affine points in natural order,
+ *   out[i] = (1/n) sum_j w^(-ij) in[j],   w the generator of fft.NewDomain(n):
+ * for in[j] = [tau^j] G that is [L_i(tau)] G, ToLagrangeG1's result, byte for byte
+ * (affine coordinates fully reduced, infinity as (0,0)).  lagrange_dev == srs_dev
+ * (in place) is allowed; the input is otherwise left unchanged.  n is a power of
+ * two, 2 <= n <= 2^min(two-adicity, 30).  Scratch (one XYZZ point per input, 144 n
+ * bytes for BN254 and 224 n for BLS12-377, plus 32 n of twiddles) comes from the
+ * context's workspace.  G1 only.  GM_ERR_INVALID: a NULL argument, an unknown
+ * curve, n out of range, the two ranges overlapping without being equal.
+ *
+ * gm_plonk_sigma is computePermutationPolynomials (setup.go:330-374) on gnark's
+ * trace.S as it lies in memory: perm_host holds 3n int64, and
+ *   s_k[i] = g^(S / n) w^(S mod n),  S = perm_host[k n + i],  g = FrMultiplicativeGen,
+ * n Montgomery fr.Elements each, fully reduced, Lagrange regular: what
+ * gm_plonk_perm_in and gm_plonk_pk_host take.  Every entry is checked against
+ * 0 <= S < 3n on the host before any device call and gm_last_error names the first
+ * offender; that S is a permutation is not checked (gnark does not either).  n as
+ * above.  GM_ERR_INVALID: a NULL argument, an unknown curve, n out of range, an
+ * entry out of range.
+ *
+ * gm_plonk_pk_setup makes the resident key from what Setup holds: the selector
+ * polynomials as gm_plonk_pk_host has them, trace.S and the canonical SRS.  It
+ * derives the Lagrange SRS from the first n canonical points and s1, s2, s3 from
+ * the permutation, and then does what gm_plonk_pk_upload does, with the same
+ * flags: the key is the same object (same gm_plonk_pk_bytes, same session outputs,
+ * same lifetime rules).  vk_digests (host, 8 + nb_bsb gnark G1Affine) receives
+ * commitTrace's commitments (setup.go:217-251) over the derived Lagrange SRS in
+ * the VerifyingKey's order S1 S2 S3 Ql Qr Qm Qo Qk (incomplete) Qcp_j;
+ * srs_lagrange_out (host, n gnark G1Affine, or NULL) receives the derived points,
+ * for pk.KzgLagrange.  No host pointer is kept.  GM_ERR_INVALID: everything
+ * gm_plonk_pk_upload refuses, a NULL permutation or vk_digests, a permutation
+ * entry outside [0, 3n). */
+int gm_kzg_srs_lagrange(gm_ctx* ctx, int curve, const void* srs_dev, size_t n, void* lagrange_dev);
+int gm_plonk_sigma(gm_ctx* ctx, int curve, size_t n, const int64_t* perm_host /* 3n */,
+                   void* s1_dev, void* s2_dev, void* s3_dev /* n Fr each, Lagrange regular */);
+typedef struct {
+  size_t n, nb_public;
+  const void *ql, *qr, *qm, *qo, *qk;   /* host, n Fr, Lagrange regular (qk incomplete) */
+  const int64_t* permutation;           /* host, 3n: trace.S */
+  size_t nb_bsb;
+  const void* const* qcp;               /* host array of nb_bsb host pointers, n Fr each */
+  const size_t* commitment_row;
+  const void* srs_canonical;            /* gnark G1Affine */
+  size_t srs_canonical_len;             /* >= n + 3 */
+} gm_plonk_setup_host;
+int gm_plonk_pk_setup(gm_ctx* ctx, int curve, const gm_plonk_setup_host* in, unsigned flags,
+                      gm_plonk_pk** out, void* vk_digests /* host, 8 + nb_bsb G1Affine */,
+                      void* srs_lagrange_out /* host, n G1Affine, or NULL */);
+
 /* ---- NTT (iciclegnark GenerateTwiddleFactors icicle.go:68,73;
  *      INttOnDevice :489,502; NttOnDevice :490; PolyOps :500;
  *      ReverseScalars :510; CPU twin fft.Domain.FFT/FFTInverse
