@@ -17,15 +17,26 @@ struct Arena;
 // two levels; G > 0: a middle pass splits each of the NS super-bins into its
 // 2^G coarse bins (large MSMs).  M = upper bound on the entries.  Coarse bins
 // above S2_BIG entries are split into parts.
+// Between the passes an entry is 8 bytes (bucket, value), or -- `compact` -- one
+// 32-bit word: the low kb = F + G bits of the bucket (its pass-1 bin gives the
+// rest), the point index and the sign.  sort_compact_fits is the rule; the
+// plan applies it once (msm_plan; GM_MSM_SORT_WIDE=1 forces 8 bytes).
 constexpr uint32_t S2_BIG = 1u << 16;
 constexpr uint32_t S2_STAGE = 6144;  // bins up to this many entries are sorted in LDS
 struct SortGeom {
   uint32_t T = 0, F = 0, G = 0, NC = 0, NS = 0;
   size_t M = 0;
+  bool compact = false;
 };
+// kb + vb <= 32, vb = 1 (sign) + the bits of the largest value, npts - 1
+inline bool sort_compact_fits(uint32_t F, uint32_t G, size_t npts) {
+  uint32_t vb = 1;
+  while (npts && ((npts - 1) >> (vb - 1))) vb++;
+  return F + G + vb <= 32;
+}
 // Digits (k_msm_digits output: window-major, plus the pass-1 bin counts
-// `scount`, NS words) -> sorted keys / values and offsets[0..T].  Scratch comes
-// from `arena`.
+// `scount`, NS words) -> sorted values, offsets[0..T] and, unless keys_out is
+// null, the sorted keys.  Scratch comes from `arena`.
 int msm_sort_digits(gm_ctx* ctx, Arena& arena, const SortGeom& g, size_t n, uint32_t W, uint32_t nb,
                     uint32_t shared_stride, const uint32_t* dig, const uint32_t* scount, uint32_t* keys_out,
                     uint32_t* vals_out, uint32_t* offsets);
@@ -79,7 +90,9 @@ struct MsmPlan {
   size_t npts = 0;    // points addressable through the plan (bounds check)
   int bits = 0;       // scalar bits the digits cover (FR_BITS; 127 for a GLV split)
   uint32_t wn = 0;    // first narrow window (window_geom; W when all are c bits)
-  uint32_t* keys = nullptr;     // sorted bucket keys (window-major bucket index), offsets[total] entries
+  // sorted bucket keys (window-major bucket index), offsets[total] entries; null
+  // for a plan built without them (only the lane-pair G2 kernels read keys)
+  uint32_t* keys = nullptr;
   uint32_t* vals = nullptr;     // point index | sign << 31
   uint32_t* offsets = nullptr;  // total + 1 bucket start offsets
   // Piece plan (G1 accumulation, msm_piece_plan): every non-empty bucket of len
@@ -106,9 +119,11 @@ int msm_piece_plan(gm_ctx* ctx, Arena& arena, MsmPlan& plan, uint32_t T);
 // k = k1 + k2 lambda with |k1|, |k2| < 2^127, over 2n points
 // [P_0..P_{n-1}, phi(P_0)..phi(P_{n-1})] (msm_device_launch builds them): half
 // the windows, so half the buckets to reduce, for the same number of bucket adds.
+// pieces: build the G1 piece plan; keys: write the sorted keys (needed by
+// msm_launch<C, true>; a plan that only G1 MSMs use can drop them).
 template <class C>
 int msm_plan(gm_ctx* ctx, Arena& arena, const void* scalars_dev, size_t n, const MsmPrecomp* pre,
-             MsmPlan& plan, bool glv = false, bool pieces = true);
+             MsmPlan& plan, bool glv = false, bool pieces = true, bool keys = true);
 // GLV for an MSM of n points on ctx: the context's setting (gm_set_msm_glv)
 // or, by default, on for n up to 2^21 (G1 and G2)
 bool msm_glv_on(const gm_ctx* ctx, bool g2, size_t n);

@@ -8,8 +8,9 @@
 //                       partitioned into coarse bins (bucket >> F) -- pass 1 of a
 //                       hand-written two-level counting sort (no library sort).
 //   2. k_msm_s2_*       (msm_sort.hip) each coarse bin -> its buckets: sorted
-//                       (bucket, point index | sign << 31) entries and the bucket
-//                       start offsets, written directly.
+//                       values (point index | sign << 31), the bucket start
+//                       offsets and -- for plans a G2 kernel reads -- the sorted
+//                       bucket keys, written directly.
 //   3. k_msm_accum_seg  G1: one lane per piece of the plan's piece plan (buckets
 //                       cut into ceil(len / T) pieces of nearly equal length,
 //                       sorted by length; k_msm_pp_* in msm_sort.hip): lazily
@@ -101,7 +102,10 @@ GM_HD void window_geom(uint32_t c, uint32_t wn, uint32_t w, uint32_t& off, uint3
 //                    coarse bins (a plain-layout block only touches its own
 //                    window's bins, so its write runs are long); pass 2 sorts
 //                    every coarse bin into its 2^F buckets and writes the
-//                    sorted keys / values and the bucket offsets directly.
+//                    sorted values, the bucket offsets and (G2 plans) the keys
+//                    directly.  Between the passes an entry is one 32-bit word
+//                    (low key bits, index, sign) when that fits, else 8 bytes
+//                    (SortGeom::compact, msm.hpp).
 // ---------------------------------------------------------------------------
 constexpr uint32_t DG_THREADS = 1024, DG_PPT = 4;
 
@@ -900,7 +904,7 @@ static int choose_window(size_t n, int bits) {
 // Keys, sort and bucket offsets for one scalar vector (see MsmPlan).
 template <class C>
 int msm_plan(gm_ctx* ctx, Arena& arena, const void* scalars_dev, size_t n, const MsmPrecomp* pre,
-             MsmPlan& plan, bool glv, bool pieces) {
+             MsmPlan& plan, bool glv, bool pieces, bool keys) {
   hipStream_t st = ctx->stream;
   plan = MsmPlan();
   plan.n = n;
@@ -979,9 +983,14 @@ int msm_plan(gm_ctx* ctx, Arena& arena, const void* scalars_dev, size_t n, const
     set_error("msm: too many buckets for the sort");
     return GM_ERR_INVALID;
   }
+  // 4-byte entries between the sort passes when the key bits below the pass-1
+  // bin, the sign and the largest point index fit (msm.hpp SortGeom);
+  // GM_MSM_SORT_WIDE=1 keeps 8 bytes (tests, A/B runs)
+  const char* wide = getenv("GM_MSM_SORT_WIDE");
+  sg.compact = !(wide && atoi(wide) > 0) && sort_compact_fits(sg.F, sg.G, plan.npts);
   int rc;
   DevBuf dig, keys_out, vals_out, offsets, scount;
-  if ((rc = dig.alloc(arena, sizeof(uint32_t) * M)) || (rc = keys_out.alloc(arena, sizeof(uint32_t) * M)) ||
+  if ((rc = dig.alloc(arena, sizeof(uint32_t) * M)) || (keys && (rc = keys_out.alloc(arena, sizeof(uint32_t) * M))) ||
       (rc = vals_out.alloc(arena, sizeof(uint32_t) * M + 16)) ||  // + 16: accum_piece_body's group loads
       (rc = offsets.alloc(arena, sizeof(uint32_t) * ((size_t)plan.total + 1))) ||
       (rc = scount.alloc(arena, sizeof(uint32_t) * sg.NS)))
@@ -1017,6 +1026,8 @@ int msm_plan(gm_ctx* ctx, Arena& arena, const void* scalars_dev, size_t n, const
   }
   {
     ProfScope ps(ctx, "msm_sort");
+    // the entry width taken, as a counted name (no events of its own)
+    if (ctx->profiling) ctx->stats[sg.compact ? "msm_sort_compact" : "msm_sort_wide"].count += 1;
     if ((rc = msm_sort_digits(ctx, arena, sg, n, W, plan.nb, g.shared_stride, dig.as<uint32_t>(),
                               scount.as<uint32_t>(), keys_out.as<uint32_t>(), vals_out.as<uint32_t>(),
                               offsets.as<uint32_t>())))
@@ -1183,6 +1194,9 @@ int msm_launch(gm_ctx* ctx, Arena& arena, const MsmPlan& plan, const void* point
     t.pcount = plan.pcount;
     t.pbase = plan.pbase;
     t.partb = plan.partb;
+  } else if (!plan.keys) {
+    set_error("msm: the plan has no sorted keys (built for G1 only)");
+    return GM_ERR_INVALID;
   }
   int rc;
   constexpr int WORDS = Coord<DF>::WORDS;  // u32 words of one gnark-layout coordinate
@@ -1388,7 +1402,7 @@ int msm_device_launch(gm_ctx* ctx, Arena& arena, const void* scalars_dev, const 
     pts = ipts.p;
   }
   MsmPlan plan;
-  if ((rc = msm_plan<C>(ctx, arena, scalars_dev, n, pre, plan, glv, !G2))) return rc;
+  if ((rc = msm_plan<C>(ctx, arena, scalars_dev, n, pre, plan, glv, !G2, G2))) return rc;
   // the caller's scalars (digits) and gnark-layout points (conversion) are not
   // read past this point
   if (inputs_read) GM_HIP(hipEventRecord(inputs_read, ctx->stream));
@@ -1451,6 +1465,6 @@ int msm_precompute_points(gm_ctx* ctx, const void* gnark_points, size_t n, const
   template int msm_device<C, G2>(gm_ctx*, const void*, const void*, size_t,                    \
                                  typename GroupSel<C, G2>::HF (&)[3], bool, const MsmPrecomp*);
 #define GM_MSM_INSTANTIATE_PLAN(C) \
-  template int msm_plan<C>(gm_ctx*, Arena&, const void*, size_t, const MsmPrecomp*, MsmPlan&, bool, bool);
+  template int msm_plan<C>(gm_ctx*, Arena&, const void*, size_t, const MsmPrecomp*, MsmPlan&, bool, bool, bool);
 
 }  // namespace gm

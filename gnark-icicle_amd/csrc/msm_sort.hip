@@ -8,7 +8,7 @@
 //   k_msm_s1_scan     one block: exclusive scan of the NC coarse counts, and the
 //                     part table -- a coarse bin above S2_BIG entries (skewed
 //                     scalars, e.g. boolean witness wires) is split into parts.
-//   k_msm_s1_scatter  digits -> coarse bins (8-B entries bucket | value << 32).
+//   k_msm_s1_scatter  digits -> coarse bins (entries: SortEnt below).
 //   k_msm_s2_local    one block per part.  A single-part bin is finished here:
 //                     LDS histogram of its 2^F buckets, LDS scan, offsets[];
 //                     a bin of <= S2_STAGE entries (the usual case: ~4K) is held
@@ -19,12 +19,39 @@
 //   k_msm_s2_scan     split bins: scan of fcount -> offsets and cursors.
 //   k_msm_s2_scatter  split bins: per part, one global range reservation per
 //                     bucket, then the scatter.
-// Traffic per entry: 8 B written in pass 1; 8 B read + 8 B written here (staged bins).
+// An entry between the passes sits in its pass-1 bin, so its position already
+// gives the key bits above kb = F + G; the final pass rebuilds a bucket from its
+// coarse bin and the low F bits.  When kb + vb <= 32 (vb = value bits: sign +
+// point index, SortGeom::compact) an entry is one 32-bit word, else 8 bytes.
+// The sorted keys are written only for plans a lane-pair (G2) kernel reads.
+// Traffic per entry: 4 or 8 B written in pass 1; the same read here, 4 B of
+// values (+ 4 B of keys) written (staged bins).
 #include "msm.hpp"
 #include "runtime.hpp"
 #include "sort_util.hpp"
 
 namespace gm {
+
+// Entry between the passes, by its word type.  kb = F + G key bits survive in
+// the compact form; `low` holds at least those; `val` is index | sign << 31.
+template <class E>
+struct SortEnt;
+template <>
+struct SortEnt<uint64_t> {  // bucket | value << 32
+  __device__ __forceinline__ static uint64_t make(uint32_t b, uint32_t v, uint32_t) { return ((uint64_t)v << 32) | b; }
+  __device__ __forceinline__ static uint32_t low(uint64_t e) { return (uint32_t)e; }
+  __device__ __forceinline__ static uint32_t val(uint64_t e, uint32_t) { return (uint32_t)(e >> 32); }
+};
+template <>
+struct SortEnt<uint32_t> {  // bucket's low kb bits | index << kb | sign << 31 (index < 2^(31 - kb))
+  __device__ __forceinline__ static uint32_t make(uint32_t b, uint32_t v, uint32_t kb) {
+    return (b & ((1u << kb) - 1)) | ((v & 0x7fffffffu) << kb) | (v & 0x80000000u);
+  }
+  __device__ __forceinline__ static uint32_t low(uint32_t e) { return e; }
+  __device__ __forceinline__ static uint32_t val(uint32_t e, uint32_t kb) {
+    return ((e & 0x7fffffffu) >> kb) | (e & 0x80000000u);
+  }
+};
 
 // LDS bytes one workgroup may allocate on `device` (queried once per device)
 static size_t device_lds_per_block(int device) {
@@ -68,16 +95,17 @@ static __global__ void __launch_bounds__(1024) k_msm_s1_scan(const uint32_t* __r
 
 // Pass-1 partition: block (chunk, w) moves the non-zero digits of window w of
 // S1_PTS points into the coarse bins: LDS histogram with ranks, one global range
-// reservation per touched bin, then the 8-B entries (bucket | value << 32).  In
-// the plain layout with 2^F <= nb the block touches only window w's bins
-// [h0, h0 + nh), so its LDS is small and its write runs long (S1_PTS / nh
-// entries per bin on average).
+// reservation per touched bin, then the entries (SortEnt<E>; F here is the
+// pass-1 shift, kb).  In the plain layout with 2^F <= nb the block touches only
+// window w's bins [h0, h0 + nh), so its LDS is small and its write runs long
+// (S1_PTS / nh entries per bin on average).
 constexpr uint32_t S1_PPT = 8, S1_PTS = S_THREADS * S1_PPT;
+template <class E>
 static __global__ void __launch_bounds__(1024) k_msm_s1_scatter(const uint32_t* __restrict__ dig, uint32_t n,
                                                                 uint32_t nb, uint32_t shared_stride, uint32_t F,
                                                                 uint32_t NC, uint32_t nh,
                                                                 uint32_t* __restrict__ ccursor,
-                                                                uint64_t* __restrict__ tmp) {
+                                                                E* __restrict__ tmp) {
   extern __shared__ uint32_t s1_lds[];
   uint32_t* hist = s1_lds;
   uint32_t* cur = s1_lds + nh;
@@ -103,21 +131,24 @@ static __global__ void __launch_bounds__(1024) k_msm_s1_scatter(const uint32_t* 
     const uint32_t i = base + r * S_THREADS + t;
     const uint32_t b = (dv[r] & 0x7fffffffu) + wb;
     const uint32_t v = (shared_stride ? w * shared_stride + i : i) | (dv[r] & 0x80000000u);
-    tmp[cur[(b >> F) - h0] + rk[r]] = ((uint64_t)v << 32) | b;
+    tmp[cur[(b >> F) - h0] + rk[r]] = SortEnt<E>::make(b, v, F);
   }
 }
 
 // The same partition with coalesced writes: the block's entries are first
 // sorted by bin into an LDS stage (rank + the bin's local base), then written out
-// in stage order, so consecutive lanes store consecutive 8-B entries of one
-// bin's run instead of 64 scattered 8-B stores per wave instruction.  PPT points
-// per thread (S_THREADS * PPT entries staged, 8 B each).
-template <uint32_t PPT>
+// in stage order, so consecutive lanes store consecutive entries of one
+// bin's run instead of 64 scattered stores per wave instruction.  PPT points
+// per thread (S_THREADS * PPT entries staged).  The stage always holds the
+// 8-B form: the copy loop finds an entry's bin in its full key, and narrows the
+// entry to E on the global store.  (A 4-B entry staged beside a 16-bit bin id,
+// at 8 and at 16 points per thread, measured slower: profiles/sort_compact_ab.txt.)
+template <class E, uint32_t PPT>
 static __global__ void __launch_bounds__(1024) k_msm_s1_scatter_st(const uint32_t* __restrict__ dig, uint32_t n,
                                                                    uint32_t nb, uint32_t shared_stride, uint32_t F,
                                                                    uint32_t NC, uint32_t nh,
                                                                    uint32_t* __restrict__ ccursor,
-                                                                   uint64_t* __restrict__ tmp) {
+                                                                   E* __restrict__ tmp) {
   constexpr uint32_t PTS = S_THREADS * PPT;
   extern __shared__ uint64_t s1s_lds[];
   uint64_t* stage = s1s_lds;
@@ -155,8 +186,8 @@ static __global__ void __launch_bounds__(1024) k_msm_s1_scatter_st(const uint32_
   __syncthreads();
   for (uint32_t q = t; q < total; q += S_THREADS) {
     const uint64_t e = stage[q];
-    const uint32_t h = ((uint32_t)e >> F) - h0;
-    tmp[cur[h] + (q - lb[h])] = e;
+    const uint32_t b = (uint32_t)e, h = (b >> F) - h0;
+    tmp[cur[h] + (q - lb[h])] = SortEnt<E>::make(b, (uint32_t)(e >> 32), F);
   }
 }
 
@@ -187,7 +218,8 @@ __device__ __forceinline__ void s2_locate(const uint32_t* __restrict__ pbase, ui
 // run on average).
 constexpr uint32_t SM_PART = 16384, SM_IPT = SM_PART / S_THREADS;
 
-static __global__ void __launch_bounds__(1024) k_msm_sm_count(const uint64_t* __restrict__ tmp,
+template <class E>
+static __global__ void __launch_bounds__(1024) k_msm_sm_count(const E* __restrict__ tmp,
                                                               const uint32_t* __restrict__ sbase,
                                                               const uint32_t* __restrict__ spbase, uint32_t NS,
                                                               uint32_t F, uint32_t G, uint32_t* __restrict__ ccount) {
@@ -200,7 +232,7 @@ static __global__ void __launch_bounds__(1024) k_msm_sm_count(const uint64_t* __
   const uint32_t lo = p * SM_PART, hi = min(lo + SM_PART, cnt), ng = 1u << G;
   for (uint32_t q = t; q < ng; q += S_THREADS) hist[q] = 0;
   __syncthreads();
-  for (uint32_t e = lo + t; e < hi; e += S_THREADS) lds_rank_add(hist, ((uint32_t)tmp[start + e] >> F) & (ng - 1));
+  for (uint32_t e = lo + t; e < hi; e += S_THREADS) lds_rank_add(hist, (SortEnt<E>::low(tmp[start + e]) >> F) & (ng - 1));
   __syncthreads();
   for (uint32_t q = t; q < ng; q += S_THREADS)
     if (hist[q]) atomicAdd(&ccount[(s << G) + q], hist[q]);
@@ -227,12 +259,13 @@ static __global__ void __launch_bounds__(1024) k_msm_sm_scan(const uint32_t* __r
   if (t == 0 && H0 + nh == NC) cbase[NC] = sbase[s + 1];
 }
 
-static __global__ void __launch_bounds__(1024) k_msm_sm_scatter(const uint64_t* __restrict__ tmp,
+template <class E>
+static __global__ void __launch_bounds__(1024) k_msm_sm_scatter(const E* __restrict__ tmp,
                                                                 const uint32_t* __restrict__ sbase,
                                                                 const uint32_t* __restrict__ spbase, uint32_t NS,
                                                                 uint32_t F, uint32_t G,
                                                                 uint32_t* __restrict__ ccursor,
-                                                                uint64_t* __restrict__ tmp2) {
+                                                                E* __restrict__ tmp2) {
   __shared__ uint32_t hist[1024], cur[1024], sh[2];
   const uint32_t j = blockIdx.x, t = threadIdx.x;
   if (j >= spbase[NS]) return;
@@ -242,14 +275,14 @@ static __global__ void __launch_bounds__(1024) k_msm_sm_scatter(const uint64_t* 
   const uint32_t lo = p * SM_PART, hi = min(lo + SM_PART, cnt), ng = 1u << G;
   for (uint32_t q = t; q < ng; q += S_THREADS) hist[q] = 0;
   __syncthreads();
-  uint64_t x[SM_IPT];
+  E x[SM_IPT];
   uint32_t rk[SM_IPT];
 #pragma unroll
   for (uint32_t it = 0; it < SM_IPT; it++) {
     const uint32_t e = lo + it * S_THREADS + t;
     if (e < hi) {
       x[it] = tmp[start + e];
-      rk[it] = lds_rank_add(hist, ((uint32_t)x[it] >> F) & (ng - 1));
+      rk[it] = lds_rank_add(hist, (SortEnt<E>::low(x[it]) >> F) & (ng - 1));
     }
   }
   __syncthreads();
@@ -259,7 +292,7 @@ static __global__ void __launch_bounds__(1024) k_msm_sm_scatter(const uint64_t* 
 #pragma unroll
   for (uint32_t it = 0; it < SM_IPT; it++) {
     const uint32_t e = lo + it * S_THREADS + t;
-    if (e < hi) tmp2[cur[((uint32_t)x[it] >> F) & (ng - 1)] + rk[it]] = x[it];
+    if (e < hi) tmp2[cur[(SortEnt<E>::low(x[it]) >> F) & (ng - 1)] + rk[it]] = x[it];
   }
 }
 
@@ -289,11 +322,20 @@ static __global__ void __launch_bounds__(1024) k_scan_add(uint32_t* __restrict__
   if (i == 0) out[n] = bsum[nblk];
 }
 
-// LDS layout: hist[2^F] | staged keys[S2_STAGE] | staged values[S2_STAGE].
-static __global__ void __launch_bounds__(1024) k_msm_s2_local(const uint64_t* __restrict__ tmp,
+// LDS layout: hist[2^F] | staged values[S2_STAGE] | (KEYS) staged keys[S2_STAGE].
+// kb = F + G: the key bits a compact entry carries (SortEnt); an entry's bucket
+// is its coarse bin's first bucket + its low F bits.  KEYS false: keys_out is
+// neither staged nor stored (it may be null).
+template <bool KEYS>
+constexpr size_t s2_local_lds(uint32_t nf) {
+  return sizeof(uint32_t) * (nf + (KEYS ? 2 : 1) * (size_t)S2_STAGE);
+}
+template <class E, bool KEYS>
+static __global__ void __launch_bounds__(1024) k_msm_s2_local(const E* __restrict__ tmp,
                                                               const uint32_t* __restrict__ cbase,
                                                               const uint32_t* __restrict__ pbase, uint32_t NC,
-                                                              uint32_t F, uint32_t T, uint32_t* __restrict__ fcount,
+                                                              uint32_t F, uint32_t kb, uint32_t T,
+                                                              uint32_t* __restrict__ fcount,
                                                               uint32_t* __restrict__ keys_out,
                                                               uint32_t* __restrict__ vals_out,
                                                               uint32_t* __restrict__ offsets) {
@@ -325,51 +367,51 @@ static __global__ void __launch_bounds__(1024) k_msm_s2_local(const uint64_t* __
     // whole bin in registers: local counting sort staged in LDS, then one
     // coalesced copy of the bin's sorted keys / values
     constexpr uint32_t IPT = S2_STAGE / S_THREADS;
-    uint64_t x[IPT];
+    E x[IPT];
     uint32_t rk[IPT];
 #pragma unroll
     for (uint32_t it = 0; it < IPT; it++) {
       const uint32_t e = it * S_THREADS + t;
       if (e < cnt) {
         x[it] = tmp[start + e];
-        rk[it] = lds_rank_add(hist, (uint32_t)x[it] & fmask);
+        rk[it] = lds_rank_add(hist, SortEnt<E>::low(x[it]) & fmask);
       }
     }
     block_excl_scan(hist, nf, wsum);
     for (uint32_t f = t; f < nf; f += S_THREADS) offsets[b0 + f] = start + hist[f];
-    uint32_t* sk = s2_lds + nf;
-    uint32_t* sv = sk + S2_STAGE;
+    uint32_t* sv = s2_lds + nf;
+    uint32_t* sk = sv + S2_STAGE;  // KEYS only
 #pragma unroll
     for (uint32_t it = 0; it < IPT; it++) {
       const uint32_t e = it * S_THREADS + t;
       if (e < cnt) {
-        const uint32_t b = (uint32_t)x[it];
-        const uint32_t pos = hist[b & fmask] + rk[it];
-        sk[pos] = b;
-        sv[pos] = (uint32_t)(x[it] >> 32);
+        const uint32_t f = SortEnt<E>::low(x[it]) & fmask;
+        const uint32_t pos = hist[f] + rk[it];
+        if constexpr (KEYS) sk[pos] = b0 + f;
+        sv[pos] = SortEnt<E>::val(x[it], kb);
       }
     }
     __syncthreads();
     for (uint32_t q = t; q < cnt; q += S_THREADS) {
-      keys_out[start + q] = sk[q];
+      if constexpr (KEYS) keys_out[start + q] = sk[q];
       vals_out[start + q] = sv[q];
     }
   } else if (cnt <= S2_BIG) {
     // too large to stage: two reads, scattered writes
-    for (uint32_t e = t; e < cnt; e += S_THREADS) lds_rank_add(hist, (uint32_t)tmp[start + e] & fmask);
+    for (uint32_t e = t; e < cnt; e += S_THREADS) lds_rank_add(hist, SortEnt<E>::low(tmp[start + e]) & fmask);
     block_excl_scan(hist, nf, wsum);
     for (uint32_t f = t; f < nf; f += S_THREADS) offsets[b0 + f] = start + hist[f];
     __syncthreads();
     for (uint32_t e = t; e < cnt; e += S_THREADS) {
-      const uint64_t x = tmp[start + e];
-      const uint32_t b = (uint32_t)x;
-      const uint32_t pos = start + lds_rank_add(hist, b & fmask);
-      keys_out[pos] = b;
-      vals_out[pos] = (uint32_t)(x >> 32);
+      const E x = tmp[start + e];
+      const uint32_t f = SortEnt<E>::low(x) & fmask;
+      const uint32_t pos = start + lds_rank_add(hist, f);
+      if constexpr (KEYS) keys_out[pos] = b0 + f;
+      vals_out[pos] = SortEnt<E>::val(x, kb);
     }
   } else {
     const uint32_t lo = p * S2_BIG, hi = min(lo + S2_BIG, cnt);
-    for (uint32_t e = lo + t; e < hi; e += S_THREADS) lds_rank_add(hist, (uint32_t)tmp[start + e] & fmask);
+    for (uint32_t e = lo + t; e < hi; e += S_THREADS) lds_rank_add(hist, SortEnt<E>::low(tmp[start + e]) & fmask);
     __syncthreads();
     for (uint32_t f = t; f < nf; f += S_THREADS)
       if (hist[f]) atomicAdd(&fcount[b0 + f], hist[f]);
@@ -402,10 +444,11 @@ static __global__ void __launch_bounds__(1024) k_msm_s2_scan(const uint32_t* __r
   }
 }
 
-static __global__ void __launch_bounds__(1024) k_msm_s2_scatter(const uint64_t* __restrict__ tmp,
+template <class E, bool KEYS>
+static __global__ void __launch_bounds__(1024) k_msm_s2_scatter(const E* __restrict__ tmp,
                                                                 const uint32_t* __restrict__ cbase,
                                                                 const uint32_t* __restrict__ pbase, uint32_t NC,
-                                                                uint32_t F, uint32_t T,
+                                                                uint32_t F, uint32_t kb, uint32_t T,
                                                                 uint32_t* __restrict__ fcursor,
                                                                 uint32_t* __restrict__ keys_out,
                                                                 uint32_t* __restrict__ vals_out) {
@@ -425,36 +468,33 @@ static __global__ void __launch_bounds__(1024) k_msm_s2_scatter(const uint64_t* 
     for (uint32_t q = t; q < nf; q += S_THREADS) hist[q] = 0;
     __syncthreads();
     const uint32_t lo = p * S2_BIG, hi = min(lo + S2_BIG, cnt);
-    for (uint32_t e = lo + t; e < hi; e += S_THREADS) lds_rank_add(hist, (uint32_t)tmp[start + e] & fmask);
+    for (uint32_t e = lo + t; e < hi; e += S_THREADS) lds_rank_add(hist, SortEnt<E>::low(tmp[start + e]) & fmask);
     __syncthreads();
     for (uint32_t f = t; f < nf; f += S_THREADS)
       if (hist[f]) cur[f] = atomicAdd(&fcursor[b0 + f], hist[f]);
     __syncthreads();
     for (uint32_t e = lo + t; e < hi; e += S_THREADS) {
-      const uint64_t x = tmp[start + e];
-      const uint32_t b = (uint32_t)x;
-      const uint32_t pos = lds_rank_add(cur, b & fmask);
-      keys_out[pos] = b;
-      vals_out[pos] = (uint32_t)(x >> 32);
+      const E x = tmp[start + e];
+      const uint32_t f = SortEnt<E>::low(x) & fmask;
+      const uint32_t pos = lds_rank_add(cur, f);
+      if constexpr (KEYS) keys_out[pos] = b0 + f;
+      vals_out[pos] = SortEnt<E>::val(x, kb);
     }
     __syncthreads();  // the LDS is reused by the next part
   }
 }
 
-int msm_sort_digits(gm_ctx* ctx, Arena& arena, const SortGeom& g, size_t n, uint32_t W, uint32_t nb,
-                    uint32_t shared_stride, const uint32_t* dig, const uint32_t* scount, uint32_t* keys_out,
-                    uint32_t* vals_out, uint32_t* offsets) {
-  if (g.NS == 0 || g.NS > 8192 || g.F > 13 || g.G > 10 || g.NC != (g.T + (1u << g.F) - 1) >> g.F ||
-      g.NS != (g.T + (1u << (g.F + g.G)) - 1) >> (g.F + g.G)) {
-    set_error("msm sort: bad geometry");
-    return GM_ERR_INVALID;
-  }
+// The passes for one entry width E and with (KEYS) or without the sorted keys.
+template <class E, bool KEYS>
+static int sort_passes(gm_ctx* ctx, Arena& arena, const SortGeom& g, size_t n, uint32_t W, uint32_t nb,
+                       uint32_t shared_stride, const uint32_t* dig, const uint32_t* scount, uint32_t* keys_out,
+                       uint32_t* vals_out, uint32_t* offsets) {
   hipStream_t st = ctx->stream;
   const uint32_t shift = g.F + g.G;  // pass-1 bin = b >> shift (super-bin, or coarse bin when G = 0)
   int rc;
   DevBuf sbase, scursor, spbase, tmp;
   if ((rc = sbase.alloc(arena, 4 * ((size_t)g.NS + 1))) || (rc = scursor.alloc(arena, 4 * (size_t)g.NS)) ||
-      (rc = spbase.alloc(arena, 4 * ((size_t)g.NS + 1))) || (rc = tmp.alloc(arena, 8 * g.M)))
+      (rc = spbase.alloc(arena, 4 * ((size_t)g.NS + 1))) || (rc = tmp.alloc(arena, sizeof(E) * g.M)))
     return rc;
   hipLaunchKernelGGL(k_msm_s1_scan, dim3(1), dim3(S_THREADS), 0, st, scount, g.NS, g.T, g.G ? SM_PART : S2_BIG,
                      sbase.as<uint32_t>(), scursor.as<uint32_t>(), spbase.as<uint32_t>(), offsets);
@@ -465,16 +505,16 @@ int msm_sort_digits(gm_ctx* ctx, Arena& arena, const SortGeom& g, size_t n, uint
   // per workgroup; a device with less takes the direct scatter)
   const size_t lds = 8 * (size_t)S1_PTS + sizeof(uint32_t) * (3 * (size_t)nh + 17);
   if (nh <= 4096 && lds <= device_lds_per_block(ctx->device)) {
-    hipLaunchKernelGGL(k_msm_s1_scatter_st<S1_PPT>, dim3(blocks_for(n, S1_PTS), W), dim3(S_THREADS), lds, st, dig,
-                       (uint32_t)n, nb, shared_stride, shift, g.NS, nh, scursor.as<uint32_t>(), tmp.as<uint64_t>());
+    hipLaunchKernelGGL((k_msm_s1_scatter_st<E, S1_PPT>), dim3(blocks_for(n, S1_PTS), W), dim3(S_THREADS), lds, st, dig,
+                       (uint32_t)n, nb, shared_stride, shift, g.NS, nh, scursor.as<uint32_t>(), tmp.as<E>());
     GM_HIP(hipGetLastError());
   } else {
-    hipLaunchKernelGGL(k_msm_s1_scatter, dim3(blocks_for(n, S1_PTS), W), dim3(S_THREADS), 2 * sizeof(uint32_t) * nh,
-                       st, dig, (uint32_t)n, nb, shared_stride, shift, g.NS, nh, scursor.as<uint32_t>(),
-                       tmp.as<uint64_t>());
+    hipLaunchKernelGGL(k_msm_s1_scatter<E>, dim3(blocks_for(n, S1_PTS), W), dim3(S_THREADS),
+                       2 * sizeof(uint32_t) * nh, st, dig, (uint32_t)n, nb, shared_stride, shift, g.NS, nh,
+                       scursor.as<uint32_t>(), tmp.as<E>());
   }
   // final pass input: coarse-binned entries with their bases / part table
-  const uint64_t* fin = tmp.as<uint64_t>();
+  const E* fin = tmp.as<E>();
   const uint32_t *cbase = sbase.as<uint32_t>(), *pbase = spbase.as<uint32_t>();
   if (g.G) {
     DevBuf ccount, cb, ccur, cparts, pb, bsum, tmp2;
@@ -482,7 +522,7 @@ int msm_sort_digits(gm_ctx* ctx, Arena& arena, const SortGeom& g, size_t n, uint
     if ((rc = ccount.alloc(arena, 4 * (size_t)g.NC)) || (rc = cb.alloc(arena, 4 * ((size_t)g.NC + 1))) ||
         (rc = ccur.alloc(arena, 4 * (size_t)g.NC)) || (rc = cparts.alloc(arena, 4 * (size_t)g.NC)) ||
         (rc = pb.alloc(arena, 4 * ((size_t)g.NC + 1))) || (rc = bsum.alloc(arena, 4 * ((size_t)nblk + 1))) ||
-        (rc = tmp2.alloc(arena, 8 * g.M)))
+        (rc = tmp2.alloc(arena, sizeof(E) * g.M)))
       return rc;
     if (nblk > 8192) {
       set_error("msm sort: too many coarse bins");
@@ -490,7 +530,7 @@ int msm_sort_digits(gm_ctx* ctx, Arena& arena, const SortGeom& g, size_t n, uint
     }
     const size_t mparts = (size_t)g.NS + g.M / SM_PART + 1;
     GM_HIP(hipMemsetAsync(ccount.p, 0, 4 * (size_t)g.NC, st));
-    hipLaunchKernelGGL(k_msm_sm_count, dim3((unsigned)mparts), dim3(S_THREADS), 0, st, tmp.as<uint64_t>(),
+    hipLaunchKernelGGL(k_msm_sm_count<E>, dim3((unsigned)mparts), dim3(S_THREADS), 0, st, tmp.as<E>(),
                        sbase.as<uint32_t>(), spbase.as<uint32_t>(), g.NS, g.F, g.G, ccount.as<uint32_t>());
     hipLaunchKernelGGL(k_msm_sm_scan, dim3(g.NS), dim3(S_THREADS), 0, st, ccount.as<uint32_t>(), sbase.as<uint32_t>(),
                        g.G, g.NC, cb.as<uint32_t>(), ccur.as<uint32_t>(), cparts.as<uint32_t>());
@@ -499,10 +539,10 @@ int msm_sort_digits(gm_ctx* ctx, Arena& arena, const SortGeom& g, size_t n, uint
     hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(S_THREADS), 0, st, bsum.as<uint32_t>(), nblk);
     hipLaunchKernelGGL(k_scan_add, dim3(blocks_for(g.NC, 256)), dim3(256), 0, st, pb.as<uint32_t>(), g.NC,
                        bsum.as<uint32_t>(), nblk);
-    hipLaunchKernelGGL(k_msm_sm_scatter, dim3((unsigned)mparts), dim3(S_THREADS), 0, st, tmp.as<uint64_t>(),
+    hipLaunchKernelGGL(k_msm_sm_scatter<E>, dim3((unsigned)mparts), dim3(S_THREADS), 0, st, tmp.as<E>(),
                        sbase.as<uint32_t>(), spbase.as<uint32_t>(), g.NS, g.F, g.G, ccur.as<uint32_t>(),
-                       tmp2.as<uint64_t>());
-    fin = tmp2.as<uint64_t>();
+                       tmp2.as<E>());
+    fin = tmp2.as<E>();
     cbase = cb.as<uint32_t>();
     pbase = pb.as<uint32_t>();
   }
@@ -512,16 +552,34 @@ int msm_sort_digits(gm_ctx* ctx, Arena& arena, const SortGeom& g, size_t n, uint
   // every coarse bin has >= 1 part; split bins add at most M / S2_BIG more
   const size_t maxparts = (size_t)g.NC + g.M / S2_BIG + 1;
   GM_HIP(hipMemsetAsync(fcount.p, 0, sizeof(uint32_t) * g.T, st));
-  hipLaunchKernelGGL(k_msm_s2_local, dim3((unsigned)maxparts), dim3(S_THREADS),
-                     sizeof(uint32_t) * (nfmax + 2 * S2_STAGE), st, fin, cbase, pbase, g.NC, g.F, g.T,
-                     fcount.as<uint32_t>(), keys_out, vals_out, offsets);
+  hipLaunchKernelGGL((k_msm_s2_local<E, KEYS>), dim3((unsigned)maxparts), dim3(S_THREADS), s2_local_lds<KEYS>(nfmax),
+                     st, fin, cbase, pbase, g.NC, g.F, shift, g.T, fcount.as<uint32_t>(), keys_out, vals_out, offsets);
   hipLaunchKernelGGL(k_msm_s2_scan, dim3(std::min<uint32_t>(g.NC, S2_SPLIT_GRID)), dim3(S_THREADS),
                      sizeof(uint32_t) * nfmax, st, cbase, pbase, g.NC, g.F, g.T, fcount.as<uint32_t>(), offsets);
-  hipLaunchKernelGGL(k_msm_s2_scatter, dim3((unsigned)std::min<size_t>(maxparts, S2_SPLIT_GRID)), dim3(S_THREADS),
-                     2 * sizeof(uint32_t) * nfmax, st, fin, cbase, pbase, g.NC, g.F, g.T, fcount.as<uint32_t>(),
-                     keys_out, vals_out);
+  hipLaunchKernelGGL((k_msm_s2_scatter<E, KEYS>), dim3((unsigned)std::min<size_t>(maxparts, S2_SPLIT_GRID)),
+                     dim3(S_THREADS), 2 * sizeof(uint32_t) * nfmax, st, fin, cbase, pbase, g.NC, g.F, shift, g.T,
+                     fcount.as<uint32_t>(), keys_out, vals_out);
   GM_HIP(hipGetLastError());
   return GM_OK;
+}
+
+int msm_sort_digits(gm_ctx* ctx, Arena& arena, const SortGeom& g, size_t n, uint32_t W, uint32_t nb,
+                    uint32_t shared_stride, const uint32_t* dig, const uint32_t* scount, uint32_t* keys_out,
+                    uint32_t* vals_out, uint32_t* offsets) {
+  if (g.NS == 0 || g.NS > 8192 || g.F > 13 || g.G > 10 || g.NC != (g.T + (1u << g.F) - 1) >> g.F ||
+      g.NS != (g.T + (1u << (g.F + g.G)) - 1) >> (g.F + g.G)) {
+    set_error("msm sort: bad geometry");
+    return GM_ERR_INVALID;
+  }
+  // compact entries hold F + G key bits, the sign, and an index below 2^(31 - F - G)
+  const size_t vmax = shared_stride ? (size_t)W * shared_stride : n;
+  if (g.compact && (vmax - 1) >> (31 - g.F - g.G)) {
+    set_error("msm sort: values do not fit a compact entry");
+    return GM_ERR_INVALID;
+  }
+  auto run = g.compact ? (keys_out ? sort_passes<uint32_t, true> : sort_passes<uint32_t, false>)
+                       : (keys_out ? sort_passes<uint64_t, true> : sort_passes<uint64_t, false>);
+  return run(ctx, arena, g, n, W, nb, shared_stride, dig, scount, keys_out, vals_out, offsets);
 }
 
 // ---------------------------------------------------------------------------

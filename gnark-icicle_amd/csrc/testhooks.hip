@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "curves.hpp"
+#include "msm.hpp"
 #include "runtime.hpp"
 #include "../../include/gnark_mi355x_testhooks.h"
 
@@ -123,6 +124,28 @@ int gm_test_point_op(gm_ctx* ctx, int curve, int g2, int op, const void* a_dev, 
   return g2 ? point_op_t<CurveBLS12377, true>(ctx, op, a_dev, b_dev, out_dev, n)
             : point_op_t<CurveBLS12377, false>(ctx, op, a_dev, b_dev, out_dev, n);
 }
+}
+
+extern "C++" {
+template <class C>
+static int g2_keyless_plan_t(gm_ctx* ctx, const void* scalars_dev, const void* points_dev, size_t n) {
+  Arena arena(ctx);
+  MsmPlan plan;
+  if (int rc = msm_plan<C>(ctx, arena, scalars_dev, n, nullptr, plan, false, false, false)) return rc;
+  MsmTail t;
+  const int rc = msm_launch<C, true>(ctx, arena, plan, points_dev, t);
+  GM_HIP(hipStreamSynchronize(ctx->stream));  // the plan's kernels, before the arena is released
+  return rc;
+}
+}
+
+extern "C" int gm_test_msm_g2_keyless_plan(gm_ctx* ctx, int curve, const void* scalars_dev, const void* points_dev,
+                                           size_t n) {
+  if (!ctx || !scalars_dev || !points_dev || n == 0) return GM_ERR_INVALID;
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  return curve == GM_BN254 ? g2_keyless_plan_t<CurveBN254>(ctx, scalars_dev, points_dev, n)
+                           : g2_keyless_plan_t<CurveBLS12377>(ctx, scalars_dev, points_dev, n);
 }
 
 /* The solver-side cost of staging the reference benchmark circuit's level shape

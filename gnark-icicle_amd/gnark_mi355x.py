@@ -63,7 +63,8 @@ SYMBOLS = [
     "gm_kzg_srs_lagrange", "gm_plonk_sigma", "gm_plonk_pk_setup",
 ]
 # test-only library (include/gnark_mi355x_testhooks.h, libgnark_mi355x_testhooks.so)
-TEST_SYMBOLS = ["gm_test_field_op", "gm_test_point_op", "gm_test_stage_replay_chain"]
+TEST_SYMBOLS = ["gm_test_field_op", "gm_test_point_op", "gm_test_stage_replay_chain",
+                "gm_test_msm_g2_keyless_plan"]
 TESTHOOKS_PATH = os.path.join(os.path.dirname(LIB_PATH), "libgnark_mi355x_testhooks.so")
 
 
@@ -175,6 +176,7 @@ def load_testhooks(path: str = None):
     T.gm_test_field_op.argtypes = [vp, i, i, i, vp, vp, vp, sz]
     T.gm_test_point_op.argtypes = [vp, i, i, i, vp, vp, vp, sz]
     T.gm_test_stage_replay_chain.argtypes = [vp, vp, sz, vp, vp, vp, sz, i, i, sz, ctypes.POINTER(ctypes.c_double)]
+    T.gm_test_msm_g2_keyless_plan.argtypes = [vp, i, vp, vp, sz]
     _testhooks = T
     return T
 
@@ -766,6 +768,11 @@ class Context:
         finally:
             for x in (A, B, O):
                 x.free()
+
+    def test_msm_g2_keyless_plan(self, curve, scalars: DeviceBuffer, points: DeviceBuffer, n: int):
+        """A G2 launch over a plan built without sorted keys: the launch must refuse
+        it, so this raises GmError naming the missing keys."""
+        _check(load_testhooks().gm_test_msm_g2_keyless_plan(self.handle, curve_id(curve), scalars.ptr, points.ptr, n))
 
 
 # ---------------------------------------------------------------------------

@@ -29,6 +29,12 @@ int gm_test_stage_replay_chain(gm_g16_stage* st, const void* wires, size_t nb_in
                                const void* b, const void* c, size_t nb_constraints, int mode, int abc,
                                size_t flush_at, double* ns_per_level);
 
+/* Builds the sort plan of n scalars without sorted keys (a G1-only plan) and
+ * hands it to the G2 launch, which must refuse it: returns that launch's code
+ * (GM_ERR_INVALID expected; gm_last_error names the missing keys).  points_dev
+ * holds n G2 points; nothing reads them when the launch refuses. */
+int gm_test_msm_g2_keyless_plan(gm_ctx* ctx, int curve, const void* scalars_dev, const void* points_dev, size_t n);
+
 #ifdef __cplusplus
 }
 #endif
