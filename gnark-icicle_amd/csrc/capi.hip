@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "curves.hpp"
+#include "g16_setup.hpp"
 #include "groth16.hpp"
 #include "kzg.hpp"
 #include "plonk.hpp"
@@ -1248,6 +1249,71 @@ int gm_batch_mul_base(gm_ctx* ctx, int curve, int g2, const void* base, const vo
               : batch_mul_t<CurveBN254, false>(ctx, base, sc, n, out);
   return g2 ? batch_mul_t<CurveBLS12377, true>(ctx, base, sc, n, out)
             : batch_mul_t<CurveBLS12377, false>(ctx, base, sc, n, out);
+}
+
+// ---- Groth16 setup: fixed-base batch multiplication (g16_setup.hip) --------------------
+int gm_set_fixed_base_window(gm_ctx* ctx, int c) {
+  if (!ctx) return refuse_null("gm_set_fixed_base_window");
+  if (c != 0 && (c < FIXED_BASE_C_MIN || c > FIXED_BASE_C_MAX)) {
+    set_error("gm_set_fixed_base_window: c must be 0 (the model) or in [" + std::to_string(FIXED_BASE_C_MIN) + ", " +
+              std::to_string(FIXED_BASE_C_MAX) + "]");
+    return GM_ERR_INVALID;
+  }
+  gm::CtxLock g(ctx);
+  ctx->fixed_base_c = c;
+  return GM_OK;
+}
+
+int gm_batch_mul_fixed(gm_ctx* ctx, int curve, int g2, const void* base, const void* sc, size_t n, void* out) {
+  if (!ctx || !base || (n && (!sc || !out))) return refuse_null("gm_batch_mul_fixed");
+  if (int rc = check_curve(curve)) return rc;
+  if (n >= (size_t(1) << 32)) {
+    set_error("gm_batch_mul_fixed: n must be below 2^32");
+    return GM_ERR_INVALID;
+  }
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  if (curve == GM_BN254)
+    return g2 ? batch_mul_fixed_device<CurveBN254, true>(ctx, base, sc, n, out)
+              : batch_mul_fixed_device<CurveBN254, false>(ctx, base, sc, n, out);
+  return g2 ? batch_mul_fixed_device<CurveBLS12377, true>(ctx, base, sc, n, out)
+            : batch_mul_fixed_device<CurveBLS12377, false>(ctx, base, sc, n, out);
+}
+
+// ---- Groth16 setup: the scalar side and the points (g16_setup.hip) ------------------------
+int gm_set_g16_setup_column_cut(gm_ctx* ctx, int t) {
+  if (!ctx) return refuse_null("gm_set_g16_setup_column_cut");
+  if (t < 0 || t > (1 << 30)) {
+    set_error("gm_set_g16_setup_column_cut: t must be 0 (the default) or in [1, 2^30]");
+    return GM_ERR_INVALID;
+  }
+  gm::CtxLock g(ctx);
+  ctx->g16_column_cut = t;
+  return GM_OK;
+}
+
+int gm_g16_setup_sizes(gm_ctx* ctx, const gm_r1cs* r1cs, const gm_g16_setup_in* in, size_t* nbA, size_t* nbB,
+                       size_t* nbK) {
+  if (!ctx || !r1cs || !in || !nbA || !nbB || !nbK) return refuse_null("gm_g16_setup_sizes");
+  size_t sizes[3] = {0, 0, 0};
+  if (int rc = g16_setup_run(ctx, "gm_g16_setup_sizes", r1cs, in, nullptr, sizes, 0, nullptr)) return rc;
+  *nbA = sizes[0], *nbB = sizes[1], *nbK = sizes[2];
+  return GM_OK;
+}
+
+int gm_g16_setup(gm_ctx* ctx, const gm_r1cs* r1cs, const gm_g16_setup_in* in, const gm_g16_setup_out* out) {
+  if (!ctx || !r1cs || !in || !out) return refuse_null("gm_g16_setup");
+  return g16_setup_run(ctx, "gm_g16_setup", r1cs, in, out, nullptr, 0, nullptr);
+}
+
+int gm_g16_pk_setup(gm_ctx* ctx, const gm_r1cs* r1cs, const gm_g16_setup_in* in, unsigned flags, gm_g16_pk** out,
+                    const gm_g16_setup_out* host_copy) {
+  if (!ctx || !r1cs || !in || !out) return refuse_null("gm_g16_pk_setup");
+  if (flags & ~(unsigned)(GM_PK_PRECOMPUTE | GM_PK_PRECOMPUTE_AUTO)) {
+    set_error("gm_g16_pk_setup: unknown flags");
+    return GM_ERR_INVALID;
+  }
+  return g16_setup_run(ctx, "gm_g16_pk_setup", r1cs, in, host_copy, nullptr, flags, out);
 }
 
 }  // extern "C"

@@ -32,6 +32,19 @@ struct gm_g16_pk {
   gm_g16_stage* spare_stage = nullptr;
 };
 
+// A constraint system resident on the device (r1cs.hip).
+struct gm_r1cs {
+  int curve = 0;
+  size_t nc = 0, nb_wires = 0, ncoeffs = 0;
+  uint32_t* rowptr[3] = {nullptr, nullptr, nullptr};
+  uint32_t* cid[3] = {nullptr, nullptr, nullptr};
+  uint32_t* vid[3] = {nullptr, nullptr, nullptr};
+  void* coeff_g = nullptr;  // gnark form (Montgomery, u64 limbs)
+  void* coeff_i = nullptr;  // internal form (radix 2^29)
+  size_t nnz[3] = {0, 0, 0};
+  bool has_const = false;  // some term is a constant (GM_R1CS_CONST): gnark's R1CS never has one
+};
+
 namespace gm {
 
 // point arrays of a key, in WriteDump order (marshal.go:430-444)

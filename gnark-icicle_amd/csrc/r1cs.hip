@@ -20,17 +20,6 @@
 #include "groth16.hpp"
 #include "runtime.hpp"
 
-struct gm_r1cs {
-  int curve = 0;
-  size_t nc = 0, nb_wires = 0, ncoeffs = 0;
-  uint32_t* rowptr[3] = {nullptr, nullptr, nullptr};
-  uint32_t* cid[3] = {nullptr, nullptr, nullptr};
-  uint32_t* vid[3] = {nullptr, nullptr, nullptr};
-  void* coeff_g = nullptr;  // gnark form (Montgomery, u64 limbs)
-  void* coeff_i = nullptr;  // internal form (radix 2^29)
-  size_t nnz[3] = {0, 0, 0};
-};
-
 namespace gm {
 namespace {
 
@@ -126,6 +115,7 @@ int gm_r1cs_upload(gm_ctx* ctx, int curve, size_t nb_constraints, size_t nb_wire
   // host validation: monotone row pointers, ids inside the tables (the kernel
   // indexes with them unchecked)
   size_t nnz[3];
+  bool has_const = false;
   for (int m = 0; m < 3; m++) {
     if (!rowptr[m] || rowptr[m][0] != 0) {
       set_error("r1cs upload: row pointers must start at 0");
@@ -139,6 +129,7 @@ int gm_r1cs_upload(gm_ctx* ctx, int curve, size_t nb_constraints, size_t nb_wire
     nnz[m] = rowptr[m][nb_constraints];
     if (nnz[m] && (!cid[m] || !vid[m])) return GM_ERR_INVALID;
     for (size_t q = 0; q < nnz[m]; q++) {
+      if (vid[m][q] == GM_R1CS_CONST) has_const = true;
       if (cid[m][q] >= ncoeffs || (vid[m][q] != GM_R1CS_CONST && vid[m][q] >= nb_wires)) {
         set_error("r1cs upload: term " + std::to_string(q) + " of matrix " + std::to_string(m) +
                   " has a coefficient or wire id out of range");
@@ -153,6 +144,7 @@ int gm_r1cs_upload(gm_ctx* ctx, int curve, size_t nb_constraints, size_t nb_wire
   r->nc = nb_constraints;
   r->nb_wires = nb_wires;
   r->ncoeffs = ncoeffs;
+  r->has_const = has_const;
   auto fail = [&](int code) {
     r1cs_release(r);
     return code;

@@ -84,6 +84,8 @@ struct gm_ctx {
   int msm_c_override = 0;
   int msm_glv = -1;   // GLV split of plain MSMs: -1 = default (n <= 2^21), 0 off, 1 on
   int msm_piece_len = 0;  // G1 piece length T (gm_set_msm_piece_len): 0 = the size rule
+  int fixed_base_c = 0;   // window of gm_batch_mul_fixed (gm_set_fixed_base_window): 0 = the model
+  int g16_column_cut = 0; // column length split over blocks in gm_g16_setup (gm_set_g16_setup_column_cut): 0 = default
   // workspace arena (stack-discipline scopes), plus two more for MSMs whose host
   // tail is deferred (pipelined MSMs: gm_msm_async, the Groth16 MSM sequence)
   gm::ArenaState arena;

@@ -61,6 +61,8 @@ SYMBOLS = [
     "gm_plonk_wires_upload", "gm_plonk_wires_bytes", "gm_plonk_wires_free", "gm_plonk_gather_lro",
     "gm_plonk_session_round1_witness", "gm_plonk_session_bsb22_sparse",
     "gm_kzg_srs_lagrange", "gm_plonk_sigma", "gm_plonk_pk_setup",
+    "gm_set_fixed_base_window", "gm_batch_mul_fixed",
+    "gm_set_g16_setup_column_cut", "gm_g16_setup_sizes", "gm_g16_setup", "gm_g16_pk_setup",
 ]
 # test-only library (include/gnark_mi355x_testhooks.h, libgnark_mi355x_testhooks.so)
 TEST_SYMBOLS = ["gm_test_field_op", "gm_test_point_op", "gm_test_stage_replay_chain",
@@ -155,6 +157,21 @@ PLONK_ROUND1_WITNESS_FIELDS = ("witness", "commitment_vals", "bl", "br", "bo", "
 class _PlonkRound1WitnessIn(ctypes.Structure):
     """gm_plonk_round1_witness_in (include/gnark_mi355x.h)."""
     _fields_ = [(k, ctypes.c_void_p) for k in PLONK_ROUND1_WITNESS_FIELDS]
+
+
+G16_SETUP_OUT_FIELDS = ("g1_alpha", "g1_beta", "g1_delta", "g1_A", "g1_B", "g1_Z", "g1_K", "g1_K_gamma",
+                        "g2_beta", "g2_delta", "g2_gamma", "g2_B", "infA", "infB", "k_wires")
+
+
+class _G16SetupIn(ctypes.Structure):
+    """gm_g16_setup_in (include/gnark_mi355x.h)."""
+    _fields_ = [("toxic", ctypes.c_void_p), ("nb_public", ctypes.c_size_t),
+                ("gamma_wires", ctypes.POINTER(ctypes.c_uint32)), ("nb_gamma", ctypes.c_size_t)]
+
+
+class _G16SetupOut(ctypes.Structure):
+    """gm_g16_setup_out (include/gnark_mi355x.h)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in G16_SETUP_OUT_FIELDS]
 
 
 _lib = None
@@ -294,6 +311,13 @@ def load_library(path: str = LIB_PATH):
     L.gm_kzg_srs_lagrange.argtypes = [vp, i, vp, sz, vp]
     L.gm_plonk_sigma.argtypes = [vp, i, sz, ctypes.POINTER(ctypes.c_int64), vp, vp, vp]
     L.gm_plonk_pk_setup.argtypes = [vp, i, ctypes.POINTER(_PlonkSetupHost), ctypes.c_uint, pvp, vp, vp]
+    L.gm_set_fixed_base_window.argtypes = [vp, i]
+    L.gm_batch_mul_fixed.argtypes = [vp, i, i, vp, vp, sz, vp]
+    L.gm_set_g16_setup_column_cut.argtypes = [vp, i]
+    L.gm_g16_setup_sizes.argtypes = [vp, vp, ctypes.POINTER(_G16SetupIn), psz, psz, psz]
+    L.gm_g16_setup.argtypes = [vp, vp, ctypes.POINTER(_G16SetupIn), ctypes.POINTER(_G16SetupOut)]
+    L.gm_g16_pk_setup.argtypes = [vp, vp, ctypes.POINTER(_G16SetupIn), ctypes.c_uint, pvp,
+                                  ctypes.POINTER(_G16SetupOut)]
     _lib = L
     return L
 
@@ -719,6 +743,33 @@ class Context:
                                                 n, out.ptr))
         return out
 
+    # ---- Groth16 setup: fixed-base batch multiplication ---------------------------
+    def set_fixed_base_window(self, c: int):
+        """Window of batch_mul_fixed's table, 2..16; 0 = the cost model in n."""
+        _check(load_library().gm_set_fixed_base_window(self.handle, c))
+
+    def batch_mul_fixed(self, curve, g2: bool, base: bytes, scalars: DeviceBuffer, n: int,
+                        out: DeviceBuffer | None = None) -> DeviceBuffer:
+        """gm_batch_mul_fixed: out[i] = [k_i] base through a window table (the bytes
+        of batch_mul_base), into out or a new buffer of n points."""
+        own = out is None
+        if own:
+            out = self.malloc(point_bytes(curve, g2) * n)
+        b = _buf(base)
+        try:
+            _check(load_library().gm_batch_mul_fixed(self.handle, curve_id(curve), int(g2), _p(b), scalars.ptr,
+                                                     n, out.ptr))
+        except GmError:
+            if own:
+                out.free()
+            raise
+        return out
+
+    def set_g16_setup_column_cut(self, t: int):
+        """Column length above which R1CS.g16_setup splits a column's sum over several
+        blocks; 0 = the default."""
+        _check(load_library().gm_set_g16_setup_column_cut(self.handle, t))
+
     # ---- PLONK setup ----------------------------------------------------------
     def kzg_srs_lagrange(self, curve, srs: DeviceBuffer, n: int, out: DeviceBuffer | None = None) -> DeviceBuffer:
         """gm_kzg_srs_lagrange: the Lagrange form of the first n points of srs (gnark
@@ -1002,6 +1053,31 @@ class ProvingKey:
             self.curve, self._h, self._keep = like.curve, like._h, like._keep
             self.n, self.nb_wires, self.nb_public, self.shard = like.n, like.nb_wires, like.nb_public, like.shard
         return self
+
+    @classmethod
+    def setup(cls, ctx: Context, r1cs: "R1CS", toxic, nb_public: int, gamma_wires=None, precompute=False,
+              host_copy: bool = False):
+        """gm_g16_pk_setup: the resident key derived on the device from the resident
+        constraint system and the toxic scalars; nothing of it crosses PCIe.  Returns
+        the key, or (key, the arrays as R1CS.g16_setup returns them) with host_copy."""
+        self = cls.__new__(cls)
+        self.ctx, self.curve = ctx, r1cs.curve
+        self._keep = self._h = None
+        handle = ctypes.c_void_p()
+        if host_copy:
+            a, o, collect, _keep = r1cs._setup_out(toxic, nb_public, gamma_wires)
+        else:
+            a, _keep = r1cs._setup_in(toxic, nb_public, gamma_wires)
+            o, collect = None, None
+        _check(load_library().gm_g16_pk_setup(ctx.handle, r1cs.handle, ctypes.byref(a), cls._flags(precompute),
+                                              ctypes.byref(handle), ctypes.byref(o) if o is not None else None))
+        self.handle = handle
+        n = 1
+        while n < r1cs.nc:
+            n <<= 1
+        self.n, self.nb_wires, self.nb_public = n, r1cs.nb_wires, nb_public
+        self.shard = (0, 1)
+        return (self, collect()) if host_copy else self
 
     def stage(self, nb_constraints: int) -> "Stage":
         return Stage(self, nb_constraints)
@@ -1449,6 +1525,61 @@ class R1CS:
 
     def eval(self, wires: DeviceBuffer, a: DeviceBuffer, b: DeviceBuffer, c: DeviceBuffer):
         _check(load_library().gm_r1cs_eval(self.ctx.handle, self.handle, wires.ptr, a.ptr, b.ptr, c.ptr))
+
+    def _setup_in(self, toxic, nb_public: int, gamma_wires):
+        a = _G16SetupIn()
+        keep = [_buf(toxic) if toxic is not None else None]
+        a.toxic = keep[0].ctypes.data if keep[0] is not None else None
+        a.nb_public = nb_public
+        if gamma_wires is not None and len(gamma_wires):
+            gw = np.ascontiguousarray(np.asarray(gamma_wires, dtype=np.uint32))
+            keep.append(gw)
+            a.gamma_wires = gw.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+            a.nb_gamma = gw.size
+        return a, keep
+
+    def g16_setup_sizes(self, toxic, nb_public: int, gamma_wires=None) -> tuple[int, int, int]:
+        """gm_g16_setup_sizes: (nbA, nbB, nbK) from the scalar side alone."""
+        a, _keep = self._setup_in(toxic, nb_public, gamma_wires)
+        n = [ctypes.c_size_t() for _ in range(3)]
+        _check(load_library().gm_g16_setup_sizes(self.ctx.handle, self.handle, ctypes.byref(a),
+                                                 *[ctypes.byref(x) for x in n]))
+        return tuple(x.value for x in n)
+
+    def _setup_out(self, toxic, nb_public: int, gamma_wires):
+        """(in struct, out struct, collect): host buffers sized by gm_g16_setup_sizes;
+        collect() turns them into the dict g16_setup returns."""
+        nbA, nbB, nbK = self.g16_setup_sizes(toxic, nb_public, gamma_wires)
+        a, keep = self._setup_in(toxic, nb_public, gamma_wires)
+        n = 1
+        while n < self.nc:
+            n <<= 1
+        g1b, g2b = point_bytes(self.curve, False), point_bytes(self.curve, True)
+        sizes = {"g1_alpha": g1b, "g1_beta": g1b, "g1_delta": g1b, "g1_A": g1b * nbA, "g1_B": g1b * nbB,
+                 "g1_Z": g1b * (n - 1), "g1_K": g1b * nbK, "g1_K_gamma": g1b * (nb_public + a.nb_gamma),
+                 "g2_beta": g2b, "g2_delta": g2b, "g2_gamma": g2b, "g2_B": g2b * nbB,
+                 "infA": self.nb_wires, "infB": self.nb_wires, "k_wires": 4 * nbK}
+        bufs = {k: np.zeros(max(v, 1), np.uint8) for k, v in sizes.items()}
+        o = _G16SetupOut()
+        for k in G16_SETUP_OUT_FIELDS:
+            setattr(o, k, bufs[k].ctypes.data)
+
+        def collect():
+            out = {k: bufs[k][:sizes[k]].tobytes() for k in G16_SETUP_OUT_FIELDS if k != "k_wires"}
+            out["k_wires"] = [int(w) for w in bufs["k_wires"][:4 * nbK].view(np.uint32)]
+            return out
+
+        return a, o, collect, keep
+
+    def g16_setup(self, toxic, nb_public: int, gamma_wires=None) -> dict:
+        """gm_g16_setup: gnark's Setup from the resident constraint system and the five
+        toxic scalars (t, alpha, beta, gamma, delta as Montgomery bytes).  Returns the
+        key's arrays as gnark-layout bytes under oracle.g16_setup's names, plus
+        g1_K_gamma (the verifier's side: public wires, then gamma_wires), g2_gamma and
+        k_wires (the wire of every g1_K point)."""
+        a, o, collect, _keep = self._setup_out(toxic, nb_public, gamma_wires)
+        _check(load_library().gm_g16_setup(self.ctx.handle, self.handle, ctypes.byref(a), ctypes.byref(o)))
+        return collect()
 
     def free(self):
         if self.handle:

@@ -854,6 +854,90 @@ int gm_jac_add(int curve, int g2, const void* p, const void* q, void* out);
 /* affine_out = p in affine form. */
 int gm_jac_to_affine(int curve, int g2, const void* p, void* affine_out);
 
+/* ---- Groth16 setup: fixed-base batch scalar multiplication ---------------------
+ * gnark-crypto's curve.BatchScalarMultiplicationG1/G2, what Setup turns its
+ * scalar vectors into points with (backend/groth16/bn254/setup.go:239-275, 318-330):
+ *   out[i] = [k_i] base
+ * The contract and the bytes are gm_batch_mul_base's: scalars_dev holds n
+ * Montgomery fr.Elements, fully reduced, on the device; out_dev receives n gnark
+ * affine points, fully reduced; infinity (k_i = 0, or base = (0,0)) is (0,0).
+ * Exactly n points are written.
+ *
+ * A window table T[w][d-1] = [d 2^(c w)] base, 1 <= d <= 2^(c-1), over the
+ * W = ceil((r bits + 1) / c) signed-digit windows of the scalar is built in the
+ * context's workspace for the call; every scalar then costs W mixed additions
+ * of gathered entries and no doubling, and the affine conversion shares one
+ * inversion per block of lanes.  c comes from a cost model in n (n W additions
+ * against W 2^(c-1) table entries), at most 16: the table is then 32 MiB for
+ * BN254 G1 and 96 MiB for BLS12-377 G2.  gm_set_fixed_base_window forces c in
+ * [2, 16] for tests and sweeps (0 = the model); the results do not depend on it.
+ * GM_ERR_INVALID: a NULL argument, an unknown curve, c out of range,
+ * n >= 2^32. */
+int gm_set_fixed_base_window(gm_ctx* ctx, int c);
+int gm_batch_mul_fixed(gm_ctx* ctx, int curve, int g2, const void* base_affine_host,
+                       const void* scalars_dev, size_t n, void* out_dev);
+
+/* ---- Groth16 setup: the scalar side and the key's points -------------------------
+ * What gnark's Setup computes between sampling the toxic waste and returning the
+ * keys (backend/groth16/bn254/setup.go:120-330, setupABC :364-445), from the
+ * resident constraint system (gm_r1cs_upload):
+ *   L_j(t) = w^j (t^n - 1) / (n (t - w^j)) for every constraint j (n = the domain:
+ *       the next power of two >= nb_constraints),
+ *   A_w = sum over the terms of L with wire w of coeff L_row(t); B_w over R, C_w over O,
+ *   InfinityA / InfinityB = exact zero tests of A_w / B_w; A, B (G1) and B (G2)
+ *       hold the non-zero ones in wire order,
+ *   K_w = (beta A_w + alpha B_w + C_w) / delta for the key's wires, / gamma for the
+ *       verifier's side: the public wires and the wires of gamma_wires (gnark's
+ *       commitment wires and private committed wires, setup.go:164-195),
+ *   Z_i = t^i (t^n - 1) / delta, bit-reversed, n - 1 of them,
+ * and every vector multiplied into its group by gm_batch_mul_fixed's kernels.
+ * The caller samples the toxic scalars (the library holds no random source) and
+ * keeps what Setup does beyond this: the Pedersen keys, vk.e, the pairing
+ * precomputation.
+ *
+ * gm_g16_setup_sizes runs the scalar side only and returns the counts the caller
+ * sizes gm_g16_setup's host buffers with: nbA and nbB points (g1_A; g1_B and
+ * g2_B), nbK (g1_K, k_wires); g1_Z holds n - 1 points, g1_K_gamma nb_public +
+ * nb_gamma, infA / infB nb_wires bytes.  A NULL member of gm_g16_setup_out is
+ * skipped.  GM_ERR_INVALID, judged on the host before any launch and named in
+ * gm_last_error: a NULL argument; nb_public > nb_wires; gamma_wires not strictly
+ * increasing inside [nb_public, nb_wires); delta = 0 or gamma = 0; t^n = 1 (the
+ * formula divides by zero); an R1CS with a constant term (GM_R1CS_CONST), which
+ * gnark's never has; more than 2^25 wires or constraints.
+ * gm_set_g16_setup_column_cut: the column length above which a column's sum is
+ * split over several blocks (0 = the default, 2^14); tests only. */
+typedef struct {
+  const void* toxic;                 /* host, 5 Fr Montgomery: t, alpha, beta, gamma, delta */
+  size_t nb_public;
+  const uint32_t* gamma_wires;       /* or NULL */
+  size_t nb_gamma;
+} gm_g16_setup_in;
+
+typedef struct {
+  /* host buffers sized by the caller from gm_g16_setup_sizes */
+  void *g1_alpha, *g1_beta, *g1_delta;
+  void *g1_A, *g1_B, *g1_Z, *g1_K;
+  void* g1_K_gamma;                  /* public wires, then gamma_wires, in wire order */
+  void *g2_beta, *g2_delta, *g2_gamma, *g2_B;
+  uint8_t *infA, *infB;
+  uint32_t* k_wires;                 /* nbK */
+} gm_g16_setup_out;
+
+int gm_set_g16_setup_column_cut(gm_ctx* ctx, int t);
+int gm_g16_setup_sizes(gm_ctx* ctx, const gm_r1cs* r1cs, const gm_g16_setup_in* in,
+                       size_t* nbA, size_t* nbB, size_t* nbK);
+int gm_g16_setup(gm_ctx* ctx, const gm_r1cs* r1cs, const gm_g16_setup_in* in,
+                 const gm_g16_setup_out* out);
+/* The resident proving key from the same derivation: the derived device arrays go
+ * through gm_g16_pk_upload_ex's own conversion (flags as there) without a trip
+ * through host memory, so the key is the object that entry makes from the arrays
+ * gm_g16_setup returns: same proofs, same gm_g16_pk_precomputed.  With host_copy
+ * non-NULL its non-NULL members also receive the arrays, as gm_g16_setup's do.  No
+ * host pointer is kept.  Refused as gm_g16_setup, and for unknown flags or fewer
+ * than two constraints. */
+int gm_g16_pk_setup(gm_ctx* ctx, const gm_r1cs* r1cs, const gm_g16_setup_in* in, unsigned flags,
+                    gm_g16_pk** out, const gm_g16_setup_out* host_copy /* or NULL */);
+
 /* ---- synthetic inputs (bench / tests; not on the hot path) ------------
  * out[i] = [k_i] base, k_i = Montgomery fr.Elements on the device, outputs
  * affine points on the device (curve.BatchScalarMultiplicationG1/G2). */
