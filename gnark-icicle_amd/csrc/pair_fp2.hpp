@@ -44,7 +44,7 @@ GM_DEV Fe<P> fe_select(bool c, const Fe<P>& a, const Fe<P>& b) {
 }
 
 // Component of a * b (Fp2 = Fp[u]/(u^2 - BETA)), inputs < 4p per component
-// with normalised limbs, result < 1.2p (BN254; ~p for BLS12-377).
+// with normalised limbs, result < 1.22p (BN254, 36 p^2 / R' + p; ~p for BLS12-377).
 //   lane 0: a0 b0 + BETA a1 b1 = a.b + (5p - ap).(|BETA| bp)
 //   lane 1: a1 b0 + a0 b1      = a.bp + ap.b
 // Lane 0's subtraction is folded into its operand (carry-free 5p - ap), so

@@ -2,10 +2,12 @@
 // parity tests to pin each arithmetic primitive against the oracle).  Not on
 // the proving path.
 #include <chrono>
+#include <initializer_list>
 #include <vector>
 
 #include "curves.hpp"
 #include "msm.hpp"
+#include "pair_fp2.hpp"
 #include "runtime.hpp"
 #include "../../include/gnark_mi355x_testhooks.h"
 
@@ -77,9 +79,377 @@ __global__ void k_point_op(int op, const uint32_t* a, const uint32_t* b, uint32_
   store_affine_gnark<F>(out + i * PW, to_affine_dev(r));
 }
 
+// ---------------------------------------------------------------------------
+// Raw-limb hooks (gm_test_field_raw_op / gm_test_point_raw_op): internal limbs
+// in and out, as they are.
+//
+// Template constants, as the library instantiates them (raw_field_valid is the
+// one list; everything else is GM_ERR_INVALID):
+//   fe_sub_lz<K>      Fr 2, 4, 8, 16, 32 (ntt.hip butterflies, B and 2B of the
+//                     growing rounds); Fp 1, 2, 4 (pf2_sqr<IN>), 8 (G1 mixed add),
+//                     10, 20 (fe2_mul_lz / fe2_sqr_lz<4>, BETA = -5)
+//   fe_sub2x_lz<K>    Fp 6 (X3 of the mixed adds)
+//   fe_sub_cf<K>      Fr 3, 5, 9, 17 (ntt.hip: 3, 5, B + 1, 2B + 1); Fp 9 (BN254
+//                     G1 mixed add; N <= 11)
+//   fe_negk_cf<K>     Fp 3 (xyzz_add_lz), 5 (G1 mixed add, pf2_mul)
+//   cneg2p + sub_lz<K> Fp 4 (G1 mixed add), 2 (lane-pair mixed add)
+//   fe_reduce_k<K>    Fr 1, 2, 4, 8, 16 (ntt.hip, plonk_lin.hip); Fp 1, 2, 4, 8
+//   fe_canon<L>       1..4
+//   fe_to2p<M>        Fp 4, 6, 8, 10, 12
+//   fe_is_zero_lz<K>  Fp 4, 6, 10
+//   fe2_sqr_lz<IN>    4;  pf2_sqr<IN>  1, 2, 4
+//   chain             0, 1, 2 for the one-lane products; 0, 1 (CH false / true)
+//                     for the lane-pair ones
+// ---------------------------------------------------------------------------
+template <class P>
+GM_DEV Fe<P> raw_load(const uint32_t* p, size_t idx) {
+  Fe<P> r;
+#pragma unroll
+  for (int k = 0; k < P::N; k++) r.v[k] = p ? p[idx * P::N + k] : 0u;
+  return r;
+}
+template <class P>
+GM_DEV void raw_store(uint32_t* p, size_t idx, const Fe<P>& a) {
+#pragma unroll
+  for (int k = 0; k < P::N; k++) p[idx * P::N + k] = a.v[k];
+}
+
+#define RAW_K(K, ...) \
+  case K: {           \
+    __VA_ARGS__;      \
+  } break;
+
+// scalar families; the ones without a CHAIN parameter live in the CH = 0 kernel
+template <class P, int CH>
+__global__ void k_field_raw_op(int fam, int par, const uint32_t* a, const uint32_t* b, const uint32_t* c,
+                               const uint32_t* d, uint32_t* out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Fe<P> x = raw_load<P>(a, i), y = raw_load<P>(b, i), z = raw_load<P>(c, i), w = raw_load<P>(d, i);
+  Fe<P> r = fe_zero<P>();
+  switch (fam) {
+    case GM_TRAW_MUL_LZ: r = fe_mul<P, false, CH>(x, y); break;
+    case GM_TRAW_SQR_LZ: r = fe_sqr<P, false, CH>(x); break;
+    case GM_TRAW_MUL: r = fe_mul<P, true, CH>(x, y); break;
+    case GM_TRAW_MUL2: r = fe_mul2_redc_u<P, CH>(x, y, z, w); break;
+    case GM_TRAW_MUL2_NEGK:
+      switch (par) {
+        RAW_K(3, r = fe_mul2_redc_u<P, CH>(x, y, fe_negk_cf<3>(z), w))
+        RAW_K(5, r = fe_mul2_redc_u<P, CH>(x, y, fe_negk_cf<5>(z), w))
+      }
+      break;
+    case GM_TRAW_SUB_CF_MUL:
+      if constexpr (P::N <= 11) {
+        switch (par) {
+          RAW_K(3, r = fe_mul<P, false, CH>(fe_sub_cf<3>(x, y), z))
+          RAW_K(5, r = fe_mul<P, false, CH>(fe_sub_cf<5>(x, y), z))
+          RAW_K(9, r = fe_mul<P, false, CH>(fe_sub_cf<9>(x, y), z))
+          RAW_K(17, r = fe_mul<P, false, CH>(fe_sub_cf<17>(x, y), z))
+        }
+      }
+      break;
+    default: break;
+  }
+  if constexpr (CH == 0) {
+    switch (fam) {
+      case GM_TRAW_ADD_LZ: r = fe_add_lz(x, y); break;
+      case GM_TRAW_SUB_LZ:
+        switch (par) {
+          RAW_K(1, r = fe_sub_lz<1>(x, y))
+          RAW_K(2, r = fe_sub_lz<2>(x, y))
+          RAW_K(4, r = fe_sub_lz<4>(x, y))
+          RAW_K(8, r = fe_sub_lz<8>(x, y))
+          RAW_K(10, r = fe_sub_lz<10>(x, y))
+          RAW_K(16, r = fe_sub_lz<16>(x, y))
+          RAW_K(20, r = fe_sub_lz<20>(x, y))
+          RAW_K(32, r = fe_sub_lz<32>(x, y))
+        }
+        break;
+      case GM_TRAW_SUB2X_LZ: r = fe_sub2x_lz<6>(x, y, z); break;
+      case GM_TRAW_CNEG_SUB:
+        switch (par) {
+          RAW_K(2, r = fe_sub_lz<2>(fe_cneg2p_cf(x, (w.v[0] & 1) != 0), y))
+          RAW_K(4, r = fe_sub_lz<4>(fe_cneg2p_cf(x, (w.v[0] & 1) != 0), y))
+        }
+        break;
+      case GM_TRAW_PMINUS: r = fe_pminus(x); break;
+      case GM_TRAW_REDUCE_K:
+        r = x;
+        switch (par) {
+          RAW_K(1, fe_reduce_k<1>(r))
+          RAW_K(2, fe_reduce_k<2>(r))
+          RAW_K(4, fe_reduce_k<4>(r))
+          RAW_K(8, fe_reduce_k<8>(r))
+          RAW_K(16, fe_reduce_k<16>(r))
+        }
+        break;
+      case GM_TRAW_CANON:
+        switch (par) {
+          RAW_K(1, r = fe_canon<1>(x))
+          RAW_K(2, r = fe_canon<2>(x))
+          RAW_K(3, r = fe_canon<3>(x))
+          RAW_K(4, r = fe_canon<4>(x))
+        }
+        break;
+      case GM_TRAW_TO2P:
+        r = x;
+        switch (par) {
+          RAW_K(4, fe_to2p<4>(r))
+          RAW_K(6, fe_to2p<6>(r))
+          RAW_K(8, fe_to2p<8>(r))
+          RAW_K(10, fe_to2p<10>(r))
+          RAW_K(12, fe_to2p<12>(r))
+        }
+        break;
+      case GM_TRAW_IS_ZERO:
+        switch (par) {
+          RAW_K(4, r.v[0] = fe_is_zero_lz<4>(x) ? 1u : 0u)
+          RAW_K(6, r.v[0] = fe_is_zero_lz<6>(x) ? 1u : 0u)
+          RAW_K(10, r.v[0] = fe_is_zero_lz<10>(x) ? 1u : 0u)
+        }
+        break;
+      case GM_TRAW_TIMES5: r = fe_times5_lz(x); break;
+      default: break;
+    }
+  }
+  raw_store<P>(out, i, r);
+}
+
+// one-lane Fp2 families and fe_mul4_redc: operands and result are 2 N limbs
+template <class P, int BETA>
+__global__ void k_field_raw_fe2(int fam, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d,
+                                uint32_t* out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  using F2 = Fe2<P, BETA>;
+  const F2 x{raw_load<P>(a, 2 * i), raw_load<P>(a, 2 * i + 1)}, y{raw_load<P>(b, 2 * i), raw_load<P>(b, 2 * i + 1)};
+  F2 r{fe_zero<P>(), fe_zero<P>()};
+  switch (fam) {
+    case GM_TRAW_FE2_MUL: r = fe2_mul_lz(x, y); break;
+    case GM_TRAW_FE2_SQR: r = fe2_sqr_lz<4>(x); break;
+    case GM_TRAW_MUL4_REDC:
+      if constexpr (P::N <= 9) {
+        const F2 z{raw_load<P>(c, 2 * i), raw_load<P>(c, 2 * i + 1)}, w{raw_load<P>(d, 2 * i), raw_load<P>(d, 2 * i + 1)};
+        r.a0 = fe_mul4_redc(x.a0, x.a1, y.a0, y.a1, z.a0, z.a1, w.a0, w.a1);
+      }
+      break;
+    default: break;
+  }
+  raw_store<P>(out, 2 * i, r.a0);
+  raw_store<P>(out, 2 * i + 1, r.a1);
+}
+
+// lane-pair Fp2 families: element i on lanes 2i (a0) and 2i + 1 (a1), whole
+// pairs active (both lanes of a pair leave together)
+template <class P, int BETA, bool CH>
+__global__ void k_field_raw_pair(int fam, int par, const uint32_t* a, const uint32_t* b, const uint32_t* c,
+                                 const uint32_t* d, uint32_t* out, size_t n) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if ((t >> 1) >= n) return;
+  const Fe<P> x = raw_load<P>(a, t), y = raw_load<P>(b, t);
+  Fe<P> r = fe_zero<P>();
+  switch (fam) {
+    case GM_TRAW_PF2_MUL: r = pf2_mul<P, BETA, CH>(x, y); break;
+    case GM_TRAW_PF2_SQR:
+      switch (par) {
+        RAW_K(1, r = pf2_sqr<P, BETA, 1, CH>(x))
+        RAW_K(2, r = pf2_sqr<P, BETA, 2, CH>(x))
+        RAW_K(4, r = pf2_sqr<P, BETA, 4, CH>(x))
+      }
+      break;
+    case GM_TRAW_PF2_MUL_SUB:
+      if constexpr (P::N <= 9 && BETA == -1 && !CH) r = pf2_mul_sub(x, y, raw_load<P>(c, t), raw_load<P>(d, t));
+      break;
+    default: break;
+  }
+  raw_store<P>(out, t, r);
+}
+
+template <class P>
+GM_DEV XYZZ<Fe<P>> raw_load_xyzz(const uint32_t* p, size_t i) {
+  return {raw_load<P>(p, 4 * i), raw_load<P>(p, 4 * i + 1), raw_load<P>(p, 4 * i + 2), raw_load<P>(p, 4 * i + 3)};
+}
+template <class P, int CH>
+__global__ void k_point_raw_g1(int op, const uint32_t* acc_in, const uint32_t* other, const uint8_t* flags,
+                               uint32_t* acc_out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  XYZZ<Fe<P>> a = raw_load_xyzz<P>(acc_in, i);
+  if (op == GM_TRAW_G1_ADD_AFF) {
+    xyzz_add_aff_lz<P, CH>(a, load_affine_gnark<Fe<P>>(other + i * 2 * P::NG), (flags[i] & 1) != 0);
+  } else if constexpr (CH == 0) {
+    if (op == GM_TRAW_G1_ADD) a = xyzz_add_lz(a, raw_load_xyzz<P>(other, i));
+    else a = xyzz_canon_raw(a);
+  }
+  raw_store<P>(acc_out, 4 * i, a.x);
+  raw_store<P>(acc_out, 4 * i + 1, a.y);
+  raw_store<P>(acc_out, 4 * i + 2, a.zz);
+  raw_store<P>(acc_out, 4 * i + 3, a.zzz);
+}
+template <class P, int BETA>
+__global__ void k_point_raw_g2(const uint32_t* acc_in, const uint32_t* other, const uint8_t* flags,
+                               uint32_t* acc_out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  using F2 = Fe2<P, BETA>;
+  auto ld = [&](int k) { return F2{raw_load<P>(acc_in, 8 * i + 2 * k), raw_load<P>(acc_in, 8 * i + 2 * k + 1)}; };
+  XYZZ<F2> a{ld(0), ld(1), ld(2), ld(3)};
+  Affine<F2> p = load_affine_gnark<F2>(other + i * 4 * P::NG);
+  if (flags[i] & 1) p = aff_neg(p);
+  xyzz_add_aff_lz(a, p);
+  auto st = [&](int k, const F2& v) {
+    raw_store<P>(acc_out, 8 * i + 2 * k, v.a0);
+    raw_store<P>(acc_out, 8 * i + 2 * k + 1, v.a1);
+  };
+  st(0, a.x);
+  st(1, a.y);
+  st(2, a.zz);
+  st(3, a.zzz);
+}
+template <class P, int BETA, bool CH>
+__global__ void k_point_raw_pair(int op, const uint32_t* acc_in, const uint32_t* other, const uint8_t* flags,
+                                 uint32_t* acc_out, size_t n) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t i = t >> 1;
+  if (i >= n) return;
+  constexpr int XW = 8 * P::N;
+  PXYZZ<P> a = pxyzz_load<P>(acc_in + i * XW);
+  if (op == GM_TRAW_G2P_ADD_AFF || op == GM_TRAW_G2P_DBL_AFF) {
+    // this lane's components of the gnark-layout point (X.a0, X.a1, Y.a0, Y.a1)
+    const uint32_t* pt = other + i * 4 * P::NG + (pair_odd() ? P::NG : 0);
+    const Fe<P> px = Coord<Fe<P>>::load_internal(pt), py = Coord<Fe<P>>::load_internal(pt + 2 * P::NG);
+    if (op == GM_TRAW_G2P_ADD_AFF) {
+      pxyzz_add_aff<P, BETA, CH>(a, px, py, (flags[i] & 1) != 0);
+    } else if constexpr (!CH) {
+      a = pxyzz_dbl_aff<P, BETA>(px, py);
+    }
+  } else if constexpr (!CH) {
+    if (op == GM_TRAW_G2P_ADD) a = pxyzz_add<P, BETA>(a, pxyzz_load<P>(other + i * XW));
+    else a = pxyzz_dbl<P, BETA>(a);
+  }
+  pxyzz_store<P>(acc_out + i * XW, a);
+}
+#undef RAW_K
+
 }  // namespace gm
 
 using namespace gm;
+
+extern "C++" {
+// the (family, K, chain) combinations the library instantiates, per field
+static bool raw_in(int k, std::initializer_list<int> l) {
+  for (int v : l)
+    if (v == k) return true;
+  return false;
+}
+static bool raw_field_valid(bool fr, int N, int fam, int K, int chain) {
+  if (chain < 0 || chain > 2) return false;
+  switch (fam) {
+    case GM_TRAW_MUL_LZ: case GM_TRAW_SQR_LZ: case GM_TRAW_MUL: return K == 0;
+    case GM_TRAW_MUL2: return !fr && K == 0;
+    case GM_TRAW_MUL2_NEGK: return !fr && raw_in(K, {3, 5});
+    case GM_TRAW_ADD_LZ: return K == 0;
+    case GM_TRAW_SUB_LZ: return fr ? raw_in(K, {2, 4, 8, 16, 32}) : raw_in(K, {1, 2, 4, 8, 10, 20});
+    case GM_TRAW_SUB2X_LZ: return !fr && K == 6;
+    case GM_TRAW_SUB_CF_MUL: return N <= 11 && (fr ? raw_in(K, {3, 5, 9, 17}) : K == 9);
+    case GM_TRAW_CNEG_SUB: return !fr && raw_in(K, {2, 4});
+    case GM_TRAW_PMINUS: case GM_TRAW_TIMES5: return !fr && K == 0;
+    case GM_TRAW_REDUCE_K: return fr ? raw_in(K, {1, 2, 4, 8, 16}) : raw_in(K, {1, 2, 4, 8});
+    case GM_TRAW_CANON: return K >= 1 && K <= 4;
+    case GM_TRAW_TO2P: return !fr && raw_in(K, {4, 6, 8, 10, 12});
+    case GM_TRAW_IS_ZERO: return !fr && raw_in(K, {4, 6, 10});
+    case GM_TRAW_FE2_MUL: return !fr && K == 0;
+    case GM_TRAW_FE2_SQR: return !fr && K == 4;
+    case GM_TRAW_PF2_MUL: return !fr && K == 0 && chain <= 1;
+    case GM_TRAW_PF2_SQR: return !fr && raw_in(K, {1, 2, 4}) && chain <= 1;
+    case GM_TRAW_PF2_MUL_SUB: return !fr && N <= 9 && K == 0 && chain == 0;
+    case GM_TRAW_MUL4_REDC: return !fr && N <= 9 && K == 0;
+    default: return false;
+  }
+}
+template <class P, int BETA>
+static int field_raw_t(gm_ctx* ctx, bool fr, int fam, int K, int chain, const void* a, const void* b, const void* c,
+                       const void* d, void* out, size_t n) {
+  if (!raw_field_valid(fr, P::N, fam, K, chain)) return GM_ERR_INVALID;
+  auto A = (const uint32_t*)a, B = (const uint32_t*)b, C = (const uint32_t*)c, D = (const uint32_t*)d;
+  auto O = (uint32_t*)out;
+  const dim3 t(64), g(blocks_for(n, 64)), g2(blocks_for(2 * n, 64));
+  hipStream_t s = ctx->stream;
+  if (fam == GM_TRAW_FE2_MUL || fam == GM_TRAW_FE2_SQR || fam == GM_TRAW_MUL4_REDC) {
+    hipLaunchKernelGGL((k_field_raw_fe2<P, BETA>), g, t, 0, s, fam, A, B, C, D, O, n);
+  } else if (fam >= GM_TRAW_PF2_MUL) {
+    if (chain) hipLaunchKernelGGL((k_field_raw_pair<P, BETA, true>), g2, t, 0, s, fam, K, A, B, C, D, O, n);
+    else hipLaunchKernelGGL((k_field_raw_pair<P, BETA, false>), g2, t, 0, s, fam, K, A, B, C, D, O, n);
+  } else {
+    const bool chained = fam <= GM_TRAW_MUL2_NEGK || fam == GM_TRAW_SUB_CF_MUL;
+    const int ch = chained ? chain : 0;
+    if (ch == 0) hipLaunchKernelGGL((k_field_raw_op<P, 0>), g, t, 0, s, fam, K, A, B, C, D, O, n);
+    else if (ch == 1) hipLaunchKernelGGL((k_field_raw_op<P, 1>), g, t, 0, s, fam, K, A, B, C, D, O, n);
+    else hipLaunchKernelGGL((k_field_raw_op<P, 2>), g, t, 0, s, fam, K, A, B, C, D, O, n);
+  }
+  GM_HIP(hipGetLastError());
+  GM_HIP(hipStreamSynchronize(s));
+  return GM_OK;
+}
+template <class P, int BETA>
+static int point_raw_t(gm_ctx* ctx, int g2, int op, int chain, const void* acc_in, const void* other,
+                       const void* flags, void* acc_out, size_t n) {
+  auto A = (const uint32_t*)acc_in, B = (const uint32_t*)other;
+  auto F = (const uint8_t*)flags;
+  auto O = (uint32_t*)acc_out;
+  const dim3 t(64), g(blocks_for(n, 64)), gp(blocks_for(2 * n, 64));
+  hipStream_t s = ctx->stream;
+  const bool needs_other = op != GM_TRAW_G1_CANON && op != GM_TRAW_G2P_DBL;
+  const bool needs_flags = op == GM_TRAW_G1_ADD_AFF || op == GM_TRAW_G2_ADD_AFF || op == GM_TRAW_G2P_ADD_AFF;
+  if ((needs_other && !B) || (needs_flags && !F)) return GM_ERR_INVALID;
+  if (!g2) {
+    if (op == GM_TRAW_G1_ADD_AFF && chain == 2) {
+      hipLaunchKernelGGL((k_point_raw_g1<P, 2>), g, t, 0, s, op, A, B, F, O, n);
+    } else if (op >= GM_TRAW_G1_ADD_AFF && op <= GM_TRAW_G1_CANON && chain == 0) {
+      hipLaunchKernelGGL((k_point_raw_g1<P, 0>), g, t, 0, s, op, A, B, F, O, n);
+    } else {
+      return GM_ERR_INVALID;
+    }
+  } else if (op == GM_TRAW_G2_ADD_AFF && chain == 0) {
+    hipLaunchKernelGGL((k_point_raw_g2<P, BETA>), g, t, 0, s, A, B, F, O, n);
+  } else if (op == GM_TRAW_G2P_ADD_AFF && chain == 1) {
+    hipLaunchKernelGGL((k_point_raw_pair<P, BETA, true>), gp, t, 0, s, op, A, B, F, O, n);
+  } else if (op >= GM_TRAW_G2P_ADD_AFF && op <= GM_TRAW_G2P_DBL && chain == 0) {
+    hipLaunchKernelGGL((k_point_raw_pair<P, BETA, false>), gp, t, 0, s, op, A, B, F, O, n);
+  } else {
+    return GM_ERR_INVALID;
+  }
+  GM_HIP(hipGetLastError());
+  GM_HIP(hipStreamSynchronize(s));
+  return GM_OK;
+}
+}
+
+extern "C" {
+int gm_test_field_raw_op(gm_ctx* ctx, int curve, int kind, int op, int chain, const void* a_dev, const void* b_dev,
+                         const void* c_dev, const void* d_dev, void* out_dev, size_t n) {
+  if (!ctx || !a_dev || !out_dev || n == 0 || op < 0 || (kind != 0 && kind != 1)) return GM_ERR_INVALID;
+  if (curve != GM_BN254 && curve != GM_BLS12_377) return GM_ERR_INVALID;
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  const int fam = op / 100, K = op % 100;
+  if (curve == GM_BN254)
+    return kind == 0 ? field_raw_t<Bn254Fr, -1>(ctx, true, fam, K, chain, a_dev, b_dev, c_dev, d_dev, out_dev, n)
+                     : field_raw_t<Bn254Fp, -1>(ctx, false, fam, K, chain, a_dev, b_dev, c_dev, d_dev, out_dev, n);
+  return kind == 0 ? field_raw_t<Bls377Fr, -5>(ctx, true, fam, K, chain, a_dev, b_dev, c_dev, d_dev, out_dev, n)
+                   : field_raw_t<Bls377Fp, -5>(ctx, false, fam, K, chain, a_dev, b_dev, c_dev, d_dev, out_dev, n);
+}
+int gm_test_point_raw_op(gm_ctx* ctx, int curve, int g2, int op, int chain, const void* acc_in_dev,
+                         const void* other_dev, const void* flags_dev, void* acc_out_dev, size_t n) {
+  if (!ctx || !acc_in_dev || !acc_out_dev || n == 0) return GM_ERR_INVALID;
+  if (curve != GM_BN254 && curve != GM_BLS12_377) return GM_ERR_INVALID;
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  return curve == GM_BN254
+             ? point_raw_t<Bn254Fp, -1>(ctx, g2, op, chain, acc_in_dev, other_dev, flags_dev, acc_out_dev, n)
+             : point_raw_t<Bls377Fp, -5>(ctx, g2, op, chain, acc_in_dev, other_dev, flags_dev, acc_out_dev, n);
+}
+}
 
 extern "C++" {
 template <class C>

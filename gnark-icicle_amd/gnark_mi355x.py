@@ -66,7 +66,7 @@ SYMBOLS = [
 ]
 # test-only library (include/gnark_mi355x_testhooks.h, libgnark_mi355x_testhooks.so)
 TEST_SYMBOLS = ["gm_test_field_op", "gm_test_point_op", "gm_test_stage_replay_chain",
-                "gm_test_msm_g2_keyless_plan"]
+                "gm_test_msm_g2_keyless_plan", "gm_test_field_raw_op", "gm_test_point_raw_op"]
 TESTHOOKS_PATH = os.path.join(os.path.dirname(LIB_PATH), "libgnark_mi355x_testhooks.so")
 
 
@@ -194,6 +194,8 @@ def load_testhooks(path: str = None):
     T.gm_test_point_op.argtypes = [vp, i, i, i, vp, vp, vp, sz]
     T.gm_test_stage_replay_chain.argtypes = [vp, vp, sz, vp, vp, vp, sz, i, i, sz, ctypes.POINTER(ctypes.c_double)]
     T.gm_test_msm_g2_keyless_plan.argtypes = [vp, i, vp, vp, sz]
+    T.gm_test_field_raw_op.argtypes = [vp, i, i, i, i, vp, vp, vp, vp, vp, sz]
+    T.gm_test_point_raw_op.argtypes = [vp, i, i, i, i, vp, vp, vp, vp, sz]
     _testhooks = T
     return T
 
@@ -819,6 +821,36 @@ class Context:
         finally:
             for x in (A, B, O):
                 x.free()
+
+    def test_field_raw_op(self, curve, kind: int, op: int, chain: int, operands, n: int, out_bytes: int) -> bytes:
+        """gm_test_field_raw_op: up to four operand arrays of raw internal limbs
+        (bytes, or None for an unused one) in, out_bytes of raw limbs out."""
+        ops = list(operands) + [None] * (4 - len(operands))
+        bufs = [self.copy_to_device(x) if x is not None else None for x in ops]
+        O = self.malloc(out_bytes)
+        try:
+            _check(load_testhooks().gm_test_field_raw_op(self.handle, curve_id(curve), kind, op, chain,
+                                                       *[b.ptr if b else None for b in bufs], O.ptr, n))
+            return O.to_host()
+        finally:
+            for x in bufs + [O]:
+                if x:
+                    x.free()
+
+    def test_point_raw_op(self, curve, g2: bool, op: int, chain: int, acc_in: bytes, other, flags, n: int) -> bytes:
+        """gm_test_point_raw_op: raw XYZZ accumulators in and out (same size);
+        other: gnark-layout affine points or raw XYZZ (None where the op takes
+        none), flags: n bytes, bit 0 the digit sign (or None)."""
+        bufs = [self.copy_to_device(x) if x is not None else None for x in (acc_in, other, flags)]
+        O = self.malloc(len(acc_in))
+        try:
+            _check(load_testhooks().gm_test_point_raw_op(self.handle, curve_id(curve), int(g2), op, chain,
+                                                       *[b.ptr if b else None for b in bufs], O.ptr, n))
+            return O.to_host()
+        finally:
+            for x in bufs + [O]:
+                if x:
+                    x.free()
 
     def test_msm_g2_keyless_plan(self, curve, scalars: DeviceBuffer, points: DeviceBuffer, n: int):
         """A G2 launch over a plan built without sorted keys: the launch must refuse

@@ -20,6 +20,62 @@ int gm_test_field_op(gm_ctx* ctx, int curve, int kind, int op, const void* a_dev
 int gm_test_point_op(gm_ctx* ctx, int curve, int g2, int op, const void* a_dev,
                      const void* b_dev, void* out_dev, size_t n);
 
+/* Raw-limb hooks for the lazily reduced layer (field.hpp "Lazily reduced
+ * arithmetic", curve.hpp, pair_fp2.hpp).  Elements cross the boundary as the
+ * internal radix-2^29 limbs: N little-endian u32 per element (N = 9, or 14 for
+ * BLS12-377 Fp), loaded and stored as they are -- no form conversion, no
+ * reduction -- so the caller picks the representative v + j p going in and sees
+ * every limb coming out.
+ *
+ * Field hook: kind 0 = Fr, 1 = Fp.  op = family * 100 + K, K the function's
+ * template constant (0 where it has none); chain = 0, 1, 2 is the product's
+ * CHAIN level (ignored by functions without one).  Scalar families take the
+ * operand arrays a..d with N limbs per element and write N limbs per element;
+ * the Fp2 families (GM_TRAW_FE2_MUL and up) take and write 2 N limbs per
+ * element, component a0 then a1.  Unused operands may be NULL (read as 0).  A
+ * (family, K, chain) the library does not instantiate for that field, or that
+ * the limb-count guard of the function excludes, is GM_ERR_INVALID. */
+#define GM_TRAW_MUL_LZ 0       /* fe_mul<P, false, CH>(a, b) */
+#define GM_TRAW_SQR_LZ 1       /* fe_sqr<P, false, CH>(a) */
+#define GM_TRAW_MUL 2          /* fe_mul<P, true, CH>(a, b) */
+#define GM_TRAW_MUL2 3         /* fe_mul2_redc_u<P, CH>(a, b, c, d) */
+#define GM_TRAW_MUL2_NEGK 4    /* fe_mul2_redc_u<P, CH>(a, b, fe_negk_cf<K>(c), d) */
+#define GM_TRAW_ADD_LZ 5       /* fe_add_lz(a, b) */
+#define GM_TRAW_SUB_LZ 6       /* fe_sub_lz<K>(a, b) */
+#define GM_TRAW_SUB2X_LZ 7     /* fe_sub2x_lz<K>(a, b, c) */
+#define GM_TRAW_SUB_CF_MUL 8   /* fe_mul<P, false, CH>(fe_sub_cf<K>(a, b), c) */
+#define GM_TRAW_CNEG_SUB 9     /* fe_sub_lz<K>(fe_cneg2p_cf(a, d[0] & 1), b) */
+#define GM_TRAW_PMINUS 10      /* fe_pminus(a) */
+#define GM_TRAW_REDUCE_K 11    /* fe_reduce_k<K>(a) */
+#define GM_TRAW_CANON 12       /* fe_canon<K>(a) */
+#define GM_TRAW_TO2P 13        /* fe_to2p<K>(a) */
+#define GM_TRAW_IS_ZERO 14     /* fe_is_zero_lz<K>(a): limb 0 = 0 or 1, the rest 0 */
+#define GM_TRAW_TIMES5 15      /* fe_times5_lz(a) */
+#define GM_TRAW_FE2_MUL 16     /* one lane: fe2_mul_lz(a, b) */
+#define GM_TRAW_FE2_SQR 17     /* one lane: fe2_sqr_lz<K>(a) */
+#define GM_TRAW_PF2_MUL 18     /* lane pair: pf2_mul<P, BETA, CH>(a, b) */
+#define GM_TRAW_PF2_SQR 19     /* lane pair: pf2_sqr<P, BETA, K, CH>(a) */
+#define GM_TRAW_PF2_MUL_SUB 20 /* lane pair: pf2_mul_sub(a, b, c, d) = a b - c d */
+#define GM_TRAW_MUL4_REDC 21   /* fe_mul4_redc(a0, a1, b0, b1, c0, c1, d0, d1), result in a0's place */
+int gm_test_field_raw_op(gm_ctx* ctx, int curve, int kind, int op, int chain, const void* a_dev, const void* b_dev,
+                         const void* c_dev, const void* d_dev, void* out_dev, size_t n);
+
+/* Point hook: acc_in / acc_out are raw XYZZ accumulators, 4 N limbs (x, y, zz,
+ * zzz), 8 N for G2 in the XYZZ<Fe2> word order (x.a0, x.a1, y.a0, ...).  other
+ * is a gnark-layout affine point (the _AFF ops) or a second raw XYZZ;
+ * flags[i] & 1 is the digit sign (the point is subtracted).  chain: G1 mixed
+ * add 0 or 2, lane-pair mixed add 0 or 1, else 0. */
+#define GM_TRAW_G1_ADD_AFF 0   /* xyzz_add_aff_lz<P, CH>(acc, other, sign) */
+#define GM_TRAW_G1_ADD 1       /* xyzz_add_lz(acc, other) */
+#define GM_TRAW_G1_CANON 2     /* xyzz_canon_raw(acc) */
+#define GM_TRAW_G2_ADD_AFF 3   /* one lane: xyzz_add_aff_lz(acc, sign ? -other : other) */
+#define GM_TRAW_G2P_ADD_AFF 4  /* lane pair: pxyzz_add_aff<P, BETA, CH>(acc, other, sign) */
+#define GM_TRAW_G2P_DBL_AFF 5  /* lane pair: pxyzz_dbl_aff(other) */
+#define GM_TRAW_G2P_ADD 6      /* lane pair: pxyzz_add(acc, other) */
+#define GM_TRAW_G2P_DBL 7      /* lane pair: pxyzz_dbl(acc) */
+int gm_test_point_raw_op(gm_ctx* ctx, int curve, int g2, int op, int chain, const void* acc_in_dev,
+                         const void* other_dev, const void* flags_dev, void* acc_out_dev, size_t n);
+
 /* Replays the level shape of the reference benchmark circuit (a chain of
  * squarings: level j finishes constraint j and solves wire nb_inputs + j)
  * through gm_g16_stage_put_indexed: mode 0 one put per level and vector, mode 1

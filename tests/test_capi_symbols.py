@@ -56,6 +56,11 @@ def test_test_hooks_live_outside_the_product_library(lib):
     assert all(hasattr(t, n) for n in tests_only)
     nm = subprocess.run(["nm", "-D", "--defined-only", LIB], capture_output=True, text=True).stdout
     assert "k_field_op" not in nm and "k_point_op" not in nm
+    for kernel in ("k_field_raw_op", "k_field_raw_fe2", "k_field_raw_pair", "k_point_raw_g1", "k_point_raw_g2",
+                   "k_point_raw_pair"):
+        assert kernel not in nm, kernel
+    tnm = subprocess.run(["nm", "-D", "--defined-only", TLIB], capture_output=True, text=True).stdout
+    assert "gm_test_field_raw_op" in tnm and "gm_test_point_raw_op" in tnm
 
 
 def test_library_leaves_process_environment_alone():

@@ -2,6 +2,7 @@
 NttOnDevice / INttOnDevice, icicle.go:489-502) vs the oracle's restatement of
 gnark-crypto fft.Domain.FFT / FFTInverse (prove.go:372-378,396), all four
 orderings x coset.  Bit-exact."""
+import functools
 import itertools
 
 import numpy as np
@@ -15,7 +16,7 @@ MODES = list(itertools.product([0, 1], [0, 1], [0, 1]))  # inverse, dit, coset
 
 
 @pytest.mark.parametrize("cname", ["bn254", "bls12377"])
-@pytest.mark.parametrize("logn", [0, 1, 2, 3, 4, 5, 8, 9, 10, 11, 12, 16, 17])
+@pytest.mark.parametrize("logn", [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18])
 def test_ntt_modes_vs_oracle(gm_ctx, oracle, cname, logn):
     n = 1 << logn
     X = gm_ctx.random_scalars(cname, n, seed=0x5EED0003 + logn)
@@ -27,6 +28,54 @@ def test_ntt_modes_vs_oracle(gm_ctx, oracle, cname, logn):
         exp = oracle.fft(cname, xb, inverse, dit, coset)
         assert got == exp, (cname, logn, inverse, dit, coset)
     X.free()
+
+
+@functools.lru_cache(maxsize=2)
+def _structured_vectors(cname, logn):
+    """Vectors on which the lazily reduced butterflies reach the top of their
+    documented ranges, or carry zeros as non-zero multiples of r: constants,
+    spikes, alternations, a half-filled vector, and w^(k i), whose transform is a
+    single spike (almost every intermediate is a zero).  gnark layout bytes."""
+    c = pyref.CURVES[cname]
+    n, half = 1 << logn, 1 << (logn - 1)
+    z, o, m = (pyref.encode_fr(c, v) for v in (0, 1, c.r - 1))
+
+    def powers(k):
+        w = pow(pyref.domain_generator(c, n), k, c.r)
+        x, out = int.from_bytes(o, "little"), []      # Montgomery form is kept by a plain factor
+        for _ in range(n):
+            out.append(x.to_bytes(32, "little"))
+            x = x * w % c.r
+        return b"".join(out)
+
+    pats = {
+        "all r-1": m * n, "all 0": z * n, "all 1": o * n,
+        "r-1 at 0": m + z * (n - 1), "r-1 at n-1": z * (n - 1) + m, "r-1 at n/2": z * half + m + z * (half - 1),
+        "0, r-1, ...": (z + m) * half, "r-1, 1, ...": (m + o) * half,
+        "w^i": powers(1), "w^((n/2-1) i)": powers(half - 1), "w^((n-1) i)": powers(n - 1),
+        "r-1 then 0": m * half + z * half,
+    }
+    assert all(len(v) == 32 * n for v in pats.values())
+    if logn >= 18:  # a reduced set keeps the oracle's share of the case within a second
+        pats = {k: pats[k] for k in ("all r-1", "r-1 at n/2", "0, r-1, ...", "w^i", "r-1 then 0")}
+    return pats
+
+
+# 6, 7: one pass; 8, 12: one pass of t = 8 and 6 + 6; 13, 14, 15, 16: two passes (7 + 6, 7 + 7, 8 + 7,
+# 8 + 8); 18: three passes (6 + 6 + 6) -- every pass shape, both even widths of the growing-bound rounds
+@pytest.mark.parametrize("inverse,dit,coset", MODES)
+@pytest.mark.parametrize("logn", [6, 7, 8, 12, 13, 14, 15, 16, 18])
+@pytest.mark.parametrize("cname", ["bn254", "bls12377"])
+def test_ntt_structured_vs_oracle(gm_ctx, oracle, cname, logn, inverse, dit, coset):
+    n = 1 << logn
+    X = gm_ctx.malloc(32 * n)
+    try:
+        for name, xb in _structured_vectors(cname, logn).items():
+            X.write(xb)
+            gm_ctx.ntt(cname, X, n, inverse, dit, coset)
+            assert X.to_host() == oracle.fft(cname, xb, inverse, dit, coset), (cname, logn, name)
+    finally:
+        X.free()
 
 
 @pytest.mark.parametrize("cname", ["bn254", "bls12377"])
