@@ -19,6 +19,7 @@
 #include "plonk_session.hpp"
 #include "plonk_setup.hpp"
 #include "plonk_wires.hpp"
+#include "plonk_wires_perm.hpp"
 #include "msm.hpp"
 #include "ntt.hpp"
 #include "runtime.hpp"
@@ -1112,6 +1113,35 @@ int gm_plonk_pk_setup(gm_ctx* ctx, int curve, const gm_plonk_setup_host* in, uns
   if (!ctx || !in || !out) return refuse_null("plonk pk setup");
   if (int rc = check_curve(curve)) return rc;
   return plonk_pk_setup(ctx, curve, in, flags, out, vk_digests, srs_lagrange_out);
+}
+
+int gm_plonk_wires_permutation(gm_ctx* ctx, const gm_plonk_wires* w, int64_t* perm_dev) {
+  if (!ctx || !w || !perm_dev) return refuse_null("plonk wires permutation");
+  return plonk_wires_permutation(ctx, w, perm_dev);
+}
+
+int gm_plonk_sigma_wires(gm_ctx* ctx, int curve, const gm_plonk_wires* w, void* s1_dev, void* s2_dev, void* s3_dev) {
+  if (!ctx || !w || !s1_dev || !s2_dev || !s3_dev) return refuse_null("plonk sigma wires");
+  if (int rc = check_curve(curve)) return rc;
+  if (w->ctx != ctx) {
+    set_error("plonk sigma wires: the tables were uploaded on another context");
+    return GM_ERR_INVALID;
+  }
+  if (w->n > (size_t(1) << 30)) {
+    set_error("plonk sigma wires: n must be a power of two, 2 <= n <= 2^30");
+    return GM_ERR_INVALID;
+  }
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  return curve == GM_BN254 ? plonk_sigma_wires_device<CurveBN254>(ctx, w, s1_dev, s2_dev, s3_dev)
+                           : plonk_sigma_wires_device<CurveBLS12377>(ctx, w, s1_dev, s2_dev, s3_dev);
+}
+
+int gm_plonk_pk_setup_wires(gm_ctx* ctx, int curve, const gm_plonk_setup_host* in, const gm_plonk_wires* w,
+                            unsigned flags, gm_plonk_pk** out, void* vk_digests, void* srs_lagrange_out) {
+  if (!ctx || !in || !w || !out) return refuse_null("plonk pk setup wires");
+  if (int rc = check_curve(curve)) return rc;
+  return plonk_pk_setup_wires(ctx, curve, in, w, flags, out, vk_digests, srs_lagrange_out);
 }
 
 // ---- NTT --------------------------------------------------------------------------

@@ -43,6 +43,7 @@
 #include "ntt.hpp"
 #include "plonk_pk.hpp"
 #include "plonk_setup.hpp"
+#include "plonk_wires_perm.hpp"
 #include "runtime.hpp"
 
 namespace gm {
@@ -201,14 +202,15 @@ __global__ void __launch_bounds__(ECFFT_TPB) k_ecfft_store(const XYZZ<F>* __rest
 }
 
 // lane t: row t % n of s_(t / n).  coset1, coset2: g and g^2, gnark form.
-template <class Fr>
+// IDX: int64 (gnark's trace.S) or u32 (positions from the wire tables).
+template <class Fr, class IDX>
 __global__ void __launch_bounds__(256)
-    k_sigma(const int64_t* __restrict__ perm, const uint32_t* __restrict__ wtab, uint32_t logn, FeG<Fr> coset1,
+    k_sigma(const IDX* __restrict__ perm, const uint32_t* __restrict__ wtab, uint32_t logn, FeG<Fr> coset1,
             FeG<Fr> coset2, uint32_t* __restrict__ s1, uint32_t* __restrict__ s2, uint32_t* __restrict__ s3) {
   const size_t n = (size_t)1 << logn;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= 3 * n) return;
-  const uint64_t v = (uint64_t)perm[t];  // in [0, 3n): checked on the host
+  const uint64_t v = (uint64_t)perm[t];  // in [0, 3n): checked on the host, or a permutation by construction
   const uint64_t c = v >> logn;
   Fe<Fr> r = fe_load_g<Fr>(wtab, v & (n - 1));
   // gnark form times internal form is gnark form (field.hpp)
@@ -246,8 +248,8 @@ struct StreamDrain {
 };
 
 template <class C>
-int setup_t(gm_ctx* ctx, const gm_plonk_setup_host* in, const PlonkPkFixed& f, unsigned flags, gm_plonk_pk* pk,
-            void* vk_digests, void* srs_lagrange_out) {
+int setup_t(gm_ctx* ctx, const gm_plonk_setup_host* in, const gm_plonk_wires* w, const PlonkPkFixed& f,
+            unsigned flags, gm_plonk_pk* pk, void* vk_digests, void* srs_lagrange_out) {
   const size_t n = in->n, pb = 2 * fp_bytes(pk->curve);
   int rc;
   {
@@ -269,9 +271,11 @@ int setup_t(gm_ctx* ctx, const gm_plonk_setup_host* in, const PlonkPkFixed& f, u
     if ((rc = msm_prepare_points<C, false>(ctx, raw.p, n, pk->srs_lagrange))) return rc;
   }
   auto lag = [&](size_t k) { return const_cast<void*>(pk->lagrange(k)); };
-  if ((rc = plonk_sigma_device<C>(ctx, n, in->permutation, lag(gm_plonk_pk::LAG_S1), lag(gm_plonk_pk::LAG_S2),
-                                  lag(gm_plonk_pk::LAG_S3))))
-    return rc;
+  rc = w ? plonk_sigma_wires_device<C>(ctx, w, lag(gm_plonk_pk::LAG_S1), lag(gm_plonk_pk::LAG_S2),
+                                       lag(gm_plonk_pk::LAG_S3))
+         : plonk_sigma_device<C>(ctx, n, in->permutation, lag(gm_plonk_pk::LAG_S1), lag(gm_plonk_pk::LAG_S2),
+                                 lag(gm_plonk_pk::LAG_S3));
+  if (rc) return rc;
   return plonk_pk_finish(ctx, f, flags, pk, vk_digests);
 }
 
@@ -327,30 +331,72 @@ int plonk_perm_check(size_t n, const int64_t* perm) {
   return GM_OK;
 }
 
+// perm: 3n int64 on the host (copied into the workspace) or, with w, derived from
+// the wire tables on the device as 3n u32
 template <class C>
-int plonk_sigma_device(gm_ctx* ctx, size_t n, const int64_t* perm_host, void* s1, void* s2, void* s3) {
+static int sigma_t(gm_ctx* ctx, size_t n, const int64_t* perm_host, const gm_plonk_wires* w, void* s1, void* s2,
+                   void* s3) {
   using Fr = typename C::Fr;
   using HF = host::F<typename C::HFr>;
   const int logn = log2_of(n);
   if (logn < 1 || logn > ecfft_max_logn<C>())
     return refuse("sigma needs n a power of two, 2 <= n <= 2^" + std::to_string(ecfft_max_logn<C>()));
-  HF w;
+  HF wn;
   int rc;
-  if ((rc = ntt_root<C>(logn, w.v))) return rc;
+  if ((rc = ntt_root<C>(logn, wn.v))) return rc;
   const HF g = host::from_u64<typename C::HFr>(C::COSET_GEN);
   Arena arena(ctx);
   DevBuf perm, wtab;
-  if ((rc = perm.alloc(arena, sizeof(int64_t) * 3 * n))) return rc;
+  if (!w && (rc = perm.alloc(arena, sizeof(int64_t) * 3 * n))) return rc;
   if ((rc = wtab.alloc(arena, 32 * n))) return rc;
   StreamDrain drain{ctx};
-  ProfScope ps(ctx, "plonk_sigma");
-  GM_HIP(hipMemcpyAsync(perm.p, perm_host, sizeof(int64_t) * 3 * n, hipMemcpyHostToDevice, ctx->stream));
+  ProfScope ps(ctx, w ? "plonk_sigma_wires" : "plonk_sigma");
+  const uint32_t* perm32 = nullptr;
+  if (w) {
+    if ((rc = plonk_wires_perm_queue(ctx, arena, w, nullptr, &perm32))) return rc;
+  } else {
+    GM_HIP(hipMemcpyAsync(perm.p, perm_host, sizeof(int64_t) * 3 * n, hipMemcpyHostToDevice, ctx->stream));
+  }
   hipLaunchKernelGGL((k_powers<Fr, false>), dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream,
-                     wtab.as<uint32_t>(), n, to_dev<HF, Fr>(w));
-  hipLaunchKernelGGL(k_sigma<Fr>, dim3(blocks_for(3 * n, 256)), dim3(256), 0, ctx->stream, perm.as<int64_t>(),
-                     wtab.as<uint32_t>(), (uint32_t)logn, to_dev<HF, Fr>(g), to_dev<HF, Fr>(g * g), (uint32_t*)s1,
-                     (uint32_t*)s2, (uint32_t*)s3);
+                     wtab.as<uint32_t>(), n, to_dev<HF, Fr>(wn));
+  if (w)
+    hipLaunchKernelGGL((k_sigma<Fr, uint32_t>), dim3(blocks_for(3 * n, 256)), dim3(256), 0, ctx->stream, perm32,
+                       wtab.as<uint32_t>(), (uint32_t)logn, to_dev<HF, Fr>(g), to_dev<HF, Fr>(g * g), (uint32_t*)s1,
+                       (uint32_t*)s2, (uint32_t*)s3);
+  else
+    hipLaunchKernelGGL((k_sigma<Fr, int64_t>), dim3(blocks_for(3 * n, 256)), dim3(256), 0, ctx->stream,
+                       perm.as<int64_t>(), wtab.as<uint32_t>(), (uint32_t)logn, to_dev<HF, Fr>(g),
+                       to_dev<HF, Fr>(g * g), (uint32_t*)s1, (uint32_t*)s2, (uint32_t*)s3);
   GM_HIP(hipGetLastError());
+  return GM_OK;
+}
+
+template <class C>
+int plonk_sigma_device(gm_ctx* ctx, size_t n, const int64_t* perm_host, void* s1, void* s2, void* s3) {
+  return sigma_t<C>(ctx, n, perm_host, nullptr, s1, s2, s3);
+}
+
+template <class C>
+int plonk_sigma_wires_device(gm_ctx* ctx, const gm_plonk_wires* w, void* s1, void* s2, void* s3) {
+  return sigma_t<C>(ctx, w->n, nullptr, w, s1, s2, s3);
+}
+
+static int pk_setup_run(gm_ctx* ctx, int curve, const gm_plonk_setup_host* in, const gm_plonk_wires* w,
+                        const PlonkPkFixed& f, unsigned flags, gm_plonk_pk** out, void* vk_digests,
+                        void* srs_lagrange_out) {
+  CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  gm_plonk_pk* pk = nullptr;
+  int rc = plonk_pk_begin(ctx, curve, f, &pk);
+  if (!rc)
+    rc = curve == GM_BN254 ? setup_t<CurveBN254>(ctx, in, w, f, flags, pk, vk_digests, srs_lagrange_out)
+                           : setup_t<CurveBLS12377>(ctx, in, w, f, flags, pk, vk_digests, srs_lagrange_out);
+  if (rc) {
+    hipStreamSynchronize(ctx->stream);  // nothing queued may outlive the buffers
+    plonk_pk_release(pk);
+    return rc;
+  }
+  *out = pk;
   return GM_OK;
 }
 
@@ -361,25 +407,27 @@ int plonk_pk_setup(gm_ctx* ctx, int curve, const gm_plonk_setup_host* in, unsign
   if (int rc = plonk_pk_check(curve, f, flags, false)) return rc;
   if (!in->permutation || !vk_digests) return refuse("the permutation and vk_digests must be non-null");
   if (int rc = plonk_perm_check(in->n, in->permutation)) return rc;
-  CtxLock g(ctx);
-  GM_HIP(hipSetDevice(ctx->device));
-  gm_plonk_pk* pk = nullptr;
-  int rc = plonk_pk_begin(ctx, curve, f, &pk);
-  if (!rc)
-    rc = curve == GM_BN254 ? setup_t<CurveBN254>(ctx, in, f, flags, pk, vk_digests, srs_lagrange_out)
-                           : setup_t<CurveBLS12377>(ctx, in, f, flags, pk, vk_digests, srs_lagrange_out);
-  if (rc) {
-    hipStreamSynchronize(ctx->stream);  // nothing queued may outlive the buffers
-    plonk_pk_release(pk);
-    return rc;
-  }
-  *out = pk;
-  return GM_OK;
+  return pk_setup_run(ctx, curve, in, nullptr, f, flags, out, vk_digests, srs_lagrange_out);
+}
+
+int plonk_pk_setup_wires(gm_ctx* ctx, int curve, const gm_plonk_setup_host* in, const gm_plonk_wires* w,
+                         unsigned flags, gm_plonk_pk** out, void* vk_digests, void* srs_lagrange_out) {
+  const PlonkPkFixed f = {in->n,      in->nb_public, in->ql, in->qr, in->qm, in->qo, in->qk,
+                          in->nb_bsb, in->qcp,       in->commitment_row, in->srs_canonical, in->srs_canonical_len};
+  if (int rc = plonk_pk_check(curve, f, flags, false)) return rc;
+  if (!vk_digests) return refuse("vk_digests must be non-null");
+  if (in->permutation) return refuse("the permutation comes from the wire tables: in->permutation must be null");
+  if (w->ctx != ctx) return refuse("the wire tables were uploaded on another context");
+  if (w->n != in->n)
+    return refuse("the wire tables have n = " + std::to_string(w->n) + ", the key has n = " + std::to_string(in->n));
+  if (w->n > WIRES_PERM_MAX_N) return refuse("the permutation from the wire tables needs n <= 2^30");
+  return pk_setup_run(ctx, curve, in, w, f, flags, out, vk_digests, srs_lagrange_out);
 }
 
 #define GM_SETUP_INST(C)                                                                     \
   template int kzg_srs_lagrange_device<C>(gm_ctx*, const void*, size_t, void*);               \
-  template int plonk_sigma_device<C>(gm_ctx*, size_t, const int64_t*, void*, void*, void*);
+  template int plonk_sigma_device<C>(gm_ctx*, size_t, const int64_t*, void*, void*, void*);     \
+  template int plonk_sigma_wires_device<C>(gm_ctx*, const gm_plonk_wires*, void*, void*, void*);
 GM_SETUP_INST(CurveBN254)
 GM_SETUP_INST(CurveBLS12377)
 

@@ -23,6 +23,13 @@ int plonk_perm_check(size_t n, const int64_t* perm);
 // Returns with the stream drained.
 template <class C>
 int plonk_sigma_device(gm_ctx* ctx, size_t n, const int64_t* perm_host, void* s1, void* s2, void* s3);
+// the same from the resident wire tables: the permutation is derived on the
+// device (plonk_wires_perm.hip) and read as 32-bit positions
+template <class C>
+int plonk_sigma_wires_device(gm_ctx* ctx, const gm_plonk_wires* w, void* s1, void* s2, void* s3);
 int plonk_pk_setup(gm_ctx* ctx, int curve, const gm_plonk_setup_host* in, unsigned flags, gm_plonk_pk** out,
                    void* vk_digests, void* srs_lagrange_out);
+// plonk_pk_setup with the permutation taken from w (in->permutation is NULL)
+int plonk_pk_setup_wires(gm_ctx* ctx, int curve, const gm_plonk_setup_host* in, const gm_plonk_wires* w,
+                         unsigned flags, gm_plonk_pk** out, void* vk_digests, void* srs_lagrange_out);
 }  // namespace gm

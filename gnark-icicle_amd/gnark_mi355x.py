@@ -61,6 +61,7 @@ SYMBOLS = [
     "gm_plonk_wires_upload", "gm_plonk_wires_bytes", "gm_plonk_wires_free", "gm_plonk_gather_lro",
     "gm_plonk_session_round1_witness", "gm_plonk_session_bsb22_sparse",
     "gm_kzg_srs_lagrange", "gm_plonk_sigma", "gm_plonk_pk_setup",
+    "gm_plonk_wires_permutation", "gm_plonk_sigma_wires", "gm_plonk_pk_setup_wires",
     "gm_set_fixed_base_window", "gm_batch_mul_fixed",
     "gm_set_g16_setup_column_cut", "gm_g16_setup_sizes", "gm_g16_setup", "gm_g16_pk_setup",
 ]
@@ -313,6 +314,9 @@ def load_library(path: str = LIB_PATH):
     L.gm_kzg_srs_lagrange.argtypes = [vp, i, vp, sz, vp]
     L.gm_plonk_sigma.argtypes = [vp, i, sz, ctypes.POINTER(ctypes.c_int64), vp, vp, vp]
     L.gm_plonk_pk_setup.argtypes = [vp, i, ctypes.POINTER(_PlonkSetupHost), ctypes.c_uint, pvp, vp, vp]
+    L.gm_plonk_wires_permutation.argtypes = [vp, vp, vp]
+    L.gm_plonk_sigma_wires.argtypes = [vp, i, vp, vp, vp, vp]
+    L.gm_plonk_pk_setup_wires.argtypes = [vp, i, ctypes.POINTER(_PlonkSetupHost), vp, ctypes.c_uint, pvp, vp, vp]
     L.gm_set_fixed_base_window.argtypes = [vp, i]
     L.gm_batch_mul_fixed.argtypes = [vp, i, i, vp, vp, sz, vp]
     L.gm_set_g16_setup_column_cut.argtypes = [vp, i]
@@ -792,6 +796,19 @@ class Context:
             _check(load_library().gm_plonk_sigma(self.handle, curve_id(curve), n,
                                                  perm.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
                                                  s[0].ptr, s[1].ptr, s[2].ptr))
+        except GmError:
+            for b in s:
+                b.free()
+            raise
+        return s[0], s[1], s[2]
+
+    def plonk_sigma_wires(self, curve, wires: "PlonkWires") -> tuple[DeviceBuffer, DeviceBuffer, DeviceBuffer]:
+        """gm_plonk_sigma_wires: s1, s2, s3 from resident wire tables, the permutation
+        derived on the device."""
+        s = [self.malloc(FR_BYTES * wires.n) for _ in range(3)]
+        try:
+            _check(load_library().gm_plonk_sigma_wires(self.handle, curve_id(curve), wires.handle,
+                                                       s[0].ptr, s[1].ptr, s[2].ptr))
         except GmError:
             for b in s:
                 b.free()
@@ -1278,7 +1295,7 @@ class PlonkProvingKey:
     @classmethod
     def setup(cls, ctx: Context, curve, n: int, nb_public: int, polys: dict, permutation, qcp, commitment_row,
               srs_canonical, cache: bool = True, srs_canonical_len: int | None = None, lagrange: bool = False,
-              digests: bool = True):
+              digests: bool = True, wires: "PlonkWires | None" = None):
         """The key from what gnark's Setup holds (gm_plonk_pk_setup): polys keyed by
         PLONK_SETUP_POLYS, permutation = trace.S (3n integers), the canonical SRS
         alone.  Returns (key, the 8 + nb_bsb digests S1 S2 S3 Ql Qr Qm Qo Qk Qcp_j as
@@ -1321,12 +1338,26 @@ class PlonkProvingKey:
         dig = np.zeros(pb * (8 + self.nb_bsb), np.uint8) if digests else None
         lag = np.zeros(pb * n, np.uint8) if lagrange else None
         out = ctypes.c_void_p()
-        _check(load_library().gm_plonk_pk_setup(ctx.handle, curve_id(curve), ctypes.byref(h),
-                                                0 if cache else PLONK_PK_NO_COSET_CACHE, ctypes.byref(out),
-                                                _p(dig) if digests else None, _p(lag) if lagrange else None))
+        flags = 0 if cache else PLONK_PK_NO_COSET_CACHE
+        tail = (ctypes.byref(out), _p(dig) if digests else None, _p(lag) if lagrange else None)
+        if wires is None:
+            _check(load_library().gm_plonk_pk_setup(ctx.handle, curve_id(curve), ctypes.byref(h), flags, *tail))
+        else:
+            _check(load_library().gm_plonk_pk_setup_wires(ctx.handle, curve_id(curve), ctypes.byref(h), wires.handle,
+                                                          flags, *tail))
         self.handle = out
         db = dig.tobytes() if digests else b""
         return self, [db[i:i + pb] for i in range(0, len(db), pb)], (lag.tobytes() if lagrange else None)
+
+    @classmethod
+    def setup_from_wires(cls, ctx: Context, curve, n: int, nb_public: int, polys: dict, wires: "PlonkWires", qcp,
+                         commitment_row, srs_canonical, cache: bool = True, srs_canonical_len: int | None = None,
+                         lagrange: bool = False, digests: bool = True, permutation=None):
+        """setup() with the permutation taken from resident wire tables
+        (gm_plonk_pk_setup_wires).  permutation stays None: the call refuses one."""
+        return cls.setup(ctx, curve, n, nb_public, polys, permutation, qcp, commitment_row, srs_canonical,
+                         cache=cache, srs_canonical_len=srs_canonical_len, lagrange=lagrange, digests=digests,
+                         wires=wires)
 
     def resident_bytes(self) -> tuple[int, int]:
         """(resident bytes, coset cache bytes) of gm_plonk_pk_bytes."""
@@ -1458,6 +1489,20 @@ class PlonkWires:
         """gm_plonk_gather_lro: l[i] = witness[xa[i]], r[i] = witness[xb[i]],
         o[i] = witness[xc[i]] on resident buffers of 32-byte elements."""
         _check(load_library().gm_plonk_gather_lro(self.ctx.handle, self.handle, witness.ptr, l.ptr, r.ptr, o.ptr))
+
+    def permutation(self, out: DeviceBuffer | None = None) -> DeviceBuffer:
+        """gm_plonk_wires_permutation: gnark's trace.S (3n int64) on the device,
+        derived from the tables; np.frombuffer(buf.to_host(), np.int64) reads it."""
+        own = out is None
+        if own:
+            out = self.ctx.malloc(8 * 3 * self.n)
+        try:
+            _check(load_library().gm_plonk_wires_permutation(self.ctx.handle, self.handle, out.ptr))
+        except GmError:
+            if own:
+                out.free()
+            raise
+        return out
 
     def resident_bytes(self) -> int:
         a = ctypes.c_size_t()

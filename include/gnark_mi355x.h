@@ -577,7 +577,36 @@ int gm_plonk_session_bsb22_sparse(gm_plonk_session* s, size_t j, const uint32_t*
  * srs_lagrange_out (host, n gnark G1Affine, or NULL) receives the derived points,
  * for pk.KzgLagrange.  No host pointer is kept.  GM_ERR_INVALID: everything
  * gm_plonk_pk_upload refuses, a NULL permutation or vk_digests, a permutation
- * entry outside [0, 3n). */
+ * entry outside [0, 3n).
+ *
+ * The three _wires calls take the permutation from resident wire tables instead of
+ * a host array, so that trace.S (24 n bytes) never crosses PCIe.  gnark's
+ * buildPermutation (setup.go:271-325) reads lro = xa | xb | xc, which is a
+ * gm_plonk_wires object's tables as they lie (3n u32, every id < nb_wires), and
+ * links every position p to the largest q < p with lro[q] == lro[p], or to the
+ * largest such q overall when there is none below p.  On the device that is a
+ * stable radix sort of the positions by wire id and a link inside every run; the
+ * result equals gnark's entry for entry and is a permutation by construction.
+ * Scratch (48 n bytes of positions and keys, about 1.5 n of counters; nothing
+ * sized by nb_wires) comes from the context's workspace.  The tables are left
+ * unchanged.
+ *
+ * gm_plonk_wires_permutation is the stage call: perm_dev (device, 3n int64)
+ * receives trace.S in gnark's element type, to be copied to the host when a CPU
+ * Prove needs pk.trace.S.  It takes no curve and returns with the stream drained.
+ * GM_ERR_INVALID (before any launch): a NULL argument, tables of another context,
+ * perm_dev not 8-byte aligned or overlapping the tables, n > 2^30 (positions are
+ * 32-bit, 3 * 2^30 < 2^32).
+ *
+ * gm_plonk_sigma_wires gives the bytes gm_plonk_sigma gives for that permutation
+ * without materialising it as int64.  Refused besides the above: what
+ * gm_plonk_sigma refuses of the curve and of n.
+ *
+ * gm_plonk_pk_setup_wires is gm_plonk_pk_setup with the permutation taken from w:
+ * same flags, same key object, same vk_digests order, same srs_lagrange_out.
+ * in->permutation must be NULL (a host permutation beside the tables is refused,
+ * so that the call has one meaning), and w->n must equal in->n.  The key does not
+ * refer to the tables afterwards. */
 int gm_kzg_srs_lagrange(gm_ctx* ctx, int curve, const void* srs_dev, size_t n, void* lagrange_dev);
 int gm_plonk_sigma(gm_ctx* ctx, int curve, size_t n, const int64_t* perm_host /* 3n */,
                    void* s1_dev, void* s2_dev, void* s3_dev /* n Fr each, Lagrange regular */);
@@ -594,6 +623,11 @@ typedef struct {
 int gm_plonk_pk_setup(gm_ctx* ctx, int curve, const gm_plonk_setup_host* in, unsigned flags,
                       gm_plonk_pk** out, void* vk_digests /* host, 8 + nb_bsb G1Affine */,
                       void* srs_lagrange_out /* host, n G1Affine, or NULL */);
+int gm_plonk_wires_permutation(gm_ctx* ctx, const gm_plonk_wires* w, int64_t* perm_dev /* device, 3n */);
+int gm_plonk_sigma_wires(gm_ctx* ctx, int curve, const gm_plonk_wires* w,
+                         void* s1_dev, void* s2_dev, void* s3_dev /* n Fr each, Lagrange regular */);
+int gm_plonk_pk_setup_wires(gm_ctx* ctx, int curve, const gm_plonk_setup_host* in, const gm_plonk_wires* w,
+                            unsigned flags, gm_plonk_pk** out, void* vk_digests, void* srs_lagrange_out);
 
 /* ---- NTT (iciclegnark GenerateTwiddleFactors icicle.go:68,73;
  *      INttOnDevice :489,502; NttOnDevice :490; PolyOps :500;
