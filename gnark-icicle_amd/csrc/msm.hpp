@@ -1,5 +1,7 @@
 // MSM entry points (see msm_impl.hpp).
 #pragma once
+#include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
@@ -71,6 +73,159 @@ inline uint32_t precomp_narrow(uint32_t c, uint32_t W, int bits) {
 // Window size and copy count for a precomputed set of n points of a
 // `bits`-bit scalar field: minimises n*W accumulation adds + ~3 adds per bucket.
 MsmPrecomp msm_choose_precomp(size_t n, int bits);
+
+// ---------------------------------------------------------------------------
+// Derived geometry of one MSM, as host functions of the sizes alone: the driver
+// (msm_plan, msm_launch, msm_reduce in msm_impl.hpp) calls them, and so does the
+// host-only report gm_test_msm_geometry (testhooks.hip), which needs no device.
+// ---------------------------------------------------------------------------
+// Window size minimising a cost model in EC adds: n*W accumulation adds plus
+// ~3 adds per bucket in the reduction (W*2^(c-1) buckets), W = ceil((bits+1)/c).
+// Picks c = 16 for 2^20 BN254 points, 20 for 2^24, and c = 17 (W = 15, a full top
+// window) instead of 18 for 2^22 BLS12-377 points.
+inline int choose_window(size_t n, int bits) {
+  int best = 8;
+  double best_cost = 1e300;
+  for (int c = 8; c <= 20; c++) {
+    const double W = (double)((bits + 1 + c - 1) / c);
+    const double cost = (double)n * W + 3.0 * W * (double)(1u << (c - 1));
+    if (cost < best_cost) {
+      best_cost = cost;
+      best = c;
+    }
+  }
+  return best;
+}
+
+// What msm_plan derives from (scalars, scalar bits, layout, window override)
+// before it allocates or launches anything.
+struct MsmPlanGeom {
+  size_t n = 0;   // (virtual) points: 2 n0 for a GLV split
+  int bits = 0;   // scalar bits the digits cover (fr_bits; 127 for a GLV split)
+  uint32_t c = 0, W = 0, nb = 0, Wred = 0, total = 0;
+  uint32_t wn = 0;  // first narrow window (W when all are c bits)
+  size_t npts = 0, M = 0;
+  SortGeom sg;
+};
+// n0 scalars of an fr_bits-bit field; glv: the split layout; pre: a precomputed
+// (shared-bucket) set or null; c_override: gm_set_msm_window's value (0: the cost
+// model).  Returns null, or the text of the refusal (GM_ERR_INVALID).
+inline const char* msm_plan_geom(size_t n0, int fr_bits, bool glv, const MsmPrecomp* pre, int c_override,
+                                 MsmPlanGeom& g) {
+  g = MsmPlanGeom();
+  size_t n = n0;
+  g.bits = fr_bits;
+  if (glv) {  // virtual points: P_i and phi(P_i)
+    n = 2 * n0;
+    g.bits = 127;
+  }
+  g.n = n;
+  if (n >= (size_t(1) << 31)) return "msm: n must be < 2^31";
+  const bool shared = pre && pre->c;
+  if (shared && (pre->stride < n || (size_t)pre->W * pre->stride >= (size_t(1) << 31) || pre->narrow >= pre->W ||
+                 (size_t)pre->c * pre->W - pre->narrow < (size_t)fr_bits + 1))
+    return "msm: precomputed point set does not cover this MSM";
+  const uint32_t c = shared ? pre->c : (c_override ? (uint32_t)c_override : (uint32_t)choose_window(n, g.bits));
+  // ceil((bits+1)/c): the top signed digit never carries
+  const uint32_t W = shared ? pre->W : (uint32_t)(g.bits + 1 + c - 1) / c;
+  g.c = c;
+  g.W = W;
+  g.nb = 1u << (c - 1);
+  g.Wred = shared ? 1 : W;
+  g.total = g.Wred * g.nb;
+  g.npts = shared ? (size_t)W * pre->stride : n;
+  const size_t M = (size_t)W * n;  // upper bound on the entries: zero digits are dropped
+  g.M = M;
+  if (M >= (size_t(1) << 31)) return "msm: n * windows must be < 2^31";
+  // Sort geometry: ~2K entries per coarse bin for uniform digits (the final pass
+  // sorts a bin of up to S2_STAGE entries in LDS; the narrow top window's bins
+  // are ~2x fuller).  Pass-1 bins (b >> (F + G)) are coarsened by G until one
+  // pass-1 block (one window of S1 points in the plain layout) touches at most
+  // 512 of them (long write runs) and there are at most 8192; G > 0 adds the
+  // middle pass (msm_sort.hip).
+  SortGeom& sg = g.sg;
+  sg.T = g.total;
+  sg.M = M;
+  sg.F = 4;
+  // A GLV plan's windows are full width (|k1|, |k2| < 0.87 * 2^127: no narrow top
+  // window) with twice the entries per bucket: ~4K-entry bins keep one pass-1
+  // block within 512 bins (no middle pass) and still fit S2_STAGE.
+  // The shared-bucket (precomputed) layout takes ~1.5K-entry bins: its 2^24 sort 3.78 -> 3.34 ms, 2^20 0.28 ->
+  // 0.19 ms against ~0.75K, while ~3K are slower again (profiles/r06v_shared_sort_bins_ab.txt); the plain
+  // layout's 2^24 sort is slower with ~2K bins than ~1K (3.29 -> 3.51 ms, r06u_sort_bins_ab.txt) and with ~0.5K
+  // (3.35 -> 3.83 ms, r06w_plain_sort_bins_ab.txt).
+  const double bin_entries = glv || shared ? 4096.0 : 2048.0;
+  while (sg.F < 13 && (double)M * std::ldexp(1.0, (int)sg.F + 1) <= bin_entries * sg.T) sg.F++;
+  auto bins = [&](uint32_t sh) { return (uint32_t)(((uint64_t)sg.T + (1ull << sh) - 1) >> sh); };
+  auto touched = [&](uint32_t sh) { return shared ? bins(sh) : std::max(1u, g.nb >> sh); };
+  // GM_MSM_SORT_MING: minimum G (tests exercise the middle pass at small sizes)
+  const char* ming = getenv("GM_MSM_SORT_MING");
+  sg.G = ming ? (uint32_t)std::min(10, std::max(0, atoi(ming))) : 0u;
+  // (shared layout at 2^20: 8192 pass-1 bins with G = 0 measured 0.285 ms vs
+  // 0.315 with the middle pass -- its 109 MB of entries stay in the caches, which
+  // merge the short write runs; at 2^24, 1.6 GB, they do not: 2.4 ms per sort)
+  const uint32_t max_touched = (shared && M < (size_t(1) << 24)) ? 8192u : 512u;
+  while (sg.G < 10 && (touched(sg.F + sg.G) > max_touched || bins(sg.F + sg.G) > 8192)) sg.G++;
+  while (sg.G && sg.F + sg.G > 31) sg.G--;
+  sg.NC = bins(sg.F);
+  sg.NS = bins(sg.F + sg.G);
+  if (sg.NS > 8192) return "msm: too many buckets for the sort";
+  // 4-byte entries between the sort passes when the key bits below the pass-1
+  // bin, the sign and the largest point index fit (SortGeom);
+  // GM_MSM_SORT_WIDE=1 keeps 8 bytes (tests, A/B runs)
+  const char* wide = getenv("GM_MSM_SORT_WIDE");
+  sg.compact = !(wide && atoi(wide) > 0) && sort_compact_fits(sg.F, sg.G, g.npts);
+  g.wn = shared ? W - pre->narrow : W;
+  if (!shared && !glv) {
+    // plain layout: balance the windows (see DigitGeom, msm_impl.hpp)
+    const uint32_t narrow = c * W - (uint32_t)(g.bits + 1);
+    if (narrow < W) g.wn = W - narrow;
+  }
+  return nullptr;
+}
+
+// Level-1 segment length (buckets) of the bucket reduction and the segments per
+// window.  Measured at 2^20 (BN254 G1 / G2 / BLS12-377 G2 reduction ms): L = 1:
+// 0.83 / 4.2 / 16.9, L = 2: 0.51 / 2.6 / 9.6, L = 4: 0.36 / 1.74 / 6.05 -- the LDS
+// bit-sum trees cost more per add than the running sums.  So L grows (to 32) as
+// long as k_msm_seg keeps >= 128K threads (two waves per SIMD): 4 for 2^20 plain,
+// 16 for the one-window 2^21 buckets of a precomputed 2^24 key (segment lengths
+// 4 / 8 re-measured in the pipelined loop, profiles/r05ai_segl_ab.txt).
+inline void msm_seg_geom(uint32_t Wred, uint32_t nb, uint32_t& L, uint32_t& nseg) {
+  uint32_t Lwant = 4;
+  while (Lwant < 32 && (size_t)Wred * nb / (2 * Lwant) >= (size_t(1) << 17)) Lwant *= 2;
+  L = nb >= Lwant ? Lwant : nb;
+  nseg = nb / L;
+}
+
+// LDS tree levels of the bucket reduction over nseg segment nodes of xyzz_bytes
+// per point (sizeof(XYZZ<DF>)): level i merges groups of 2^lg[i] nodes; Q is the
+// points per node after the last level, [G, U, Y_0..Y_{Q-3}].  At most 512 tree
+// tasks (adds) per level: two per thread of a BS_THREADS block.  (A 512-thread
+// block with one task per thread measured no faster at 2^20: the tree's tail
+// is short of blocks, not of threads.)
+constexpr uint32_t BS_THREADS = 256;
+struct MsmTreeGeom {
+  static constexpr uint32_t MAX_LEVELS = 24;  // a level at least halves nseg <= 2^23
+  uint32_t levels = 0, lg[MAX_LEVELS] = {}, Q = 2;
+};
+// false: a level does not fit LDS
+inline bool msm_tree_geom(uint32_t nseg, size_t xyzz_bytes, MsmTreeGeom& g) {
+  g = MsmTreeGeom();
+  const size_t slot_budget = (96u << 10) / xyzz_bytes;
+  uint32_t m = nseg, Q = 2;
+  while (m > 1) {
+    uint32_t lg = 0;
+    // largest power-of-two group with NT*Q slots in budget and <= 2 tasks per thread
+    while ((2u << lg) <= m && (size_t)(2u << lg) * Q <= slot_budget && (1u << lg) * (Q + 1) <= 2 * BS_THREADS) lg++;
+    if (lg == 0 || g.levels == MsmTreeGeom::MAX_LEVELS) return false;
+    g.lg[g.levels++] = lg;
+    Q += lg;
+    m >>= lg;
+  }
+  g.Q = Q;
+  return true;
+}
 
 // Host wire-map sentinel "this wire has no point" (groth16.hip, the shared wire
 // plan): k_expand_points writes an all-zero (infinity) point into the expanded

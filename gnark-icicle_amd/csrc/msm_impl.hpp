@@ -789,10 +789,7 @@ __global__ void __launch_bounds__(128) k_msm_fixup_long(const uint32_t* __restri
 //   host: P_w = U + sum_b 2^(b + log2 L) Y_b, merged into the window Horner.
 // ---------------------------------------------------------------------------
 // node layout: per window, m nodes of Q = 2 + K XYZZ points [G, U, Y_0..Y_{K-1}]
-// At most 512 tree tasks (adds) per level: two per thread.  (A 512-thread
-// block with one task per thread measured no faster at 2^20: the tree's tail
-// is short of blocks, not of threads.)
-constexpr uint32_t BS_THREADS = 256;
+// (tree levels and the BS_THREADS block: msm_tree_geom, msm.hpp)
 // A bucket with no entries (offsets[b] == offsets[b + 1]) was never written by
 // the accumulation or the fixup: it reads as infinity here, so the buckets need no
 // clearing before the accumulation (a 1 GB memset per plain 2^24 MSM).
@@ -883,24 +880,7 @@ __global__ void __launch_bounds__(128) k_msm_export(const XYZZ<F>* __restrict__ 
 // ---------------------------------------------------------------------------
 // host driver
 // ---------------------------------------------------------------------------
-// Window size minimising a cost model in EC adds: n*W accumulation adds plus
-// ~3 adds per bucket in the reduction (W*2^(c-1) buckets), W = ceil((bits+1)/c).
-// Picks c = 16 for 2^20 BN254 points, 20 for 2^24, and c = 17 (W = 15, a full top
-// window) instead of 18 for 2^22 BLS12-377 points.
-static int choose_window(size_t n, int bits) {
-  int best = 8;
-  double best_cost = 1e300;
-  for (int c = 8; c <= 20; c++) {
-    const double W = (double)((bits + 1 + c - 1) / c);
-    const double cost = (double)n * W + 3.0 * W * (double)(1u << (c - 1));
-    if (cost < best_cost) {
-      best_cost = cost;
-      best = c;
-    }
-  }
-  return best;
-}
-
+// (window choice and the plan's derived sizes: choose_window, msm_plan_geom, msm.hpp)
 // Keys, sort and bucket offsets for one scalar vector (see MsmPlan).
 template <class C>
 int msm_plan(gm_ctx* ctx, Arena& arena, const void* scalars_dev, size_t n, const MsmPrecomp* pre,
@@ -915,79 +895,26 @@ int msm_plan(gm_ctx* ctx, Arena& arena, const void* scalars_dev, size_t n, const
     return GM_ERR_INVALID;
   }
   const size_t n0 = n;  // scalars
-  if (glv) {            // virtual points: P_i and phi(P_i)
-    n = 2 * n0;
-    plan.n = n;
-    plan.bits = 127;
-  }
-  if (n >= (size_t(1) << 31)) {
-    set_error("msm: n must be < 2^31");
+  MsmPlanGeom pg;
+  const char* refusal = msm_plan_geom(n0, C::FR_BITS, glv, pre, ctx->msm_c_override, pg);
+  n = pg.n;  // GLV: the virtual points P_i and phi(P_i)
+  plan.n = pg.n;
+  plan.bits = pg.bits;
+  plan.c = pg.c;
+  plan.W = pg.W;
+  plan.nb = pg.nb;
+  plan.Wred = pg.Wred;
+  plan.total = pg.total;
+  plan.npts = pg.npts;
+  plan.M = pg.M;
+  if (refusal) {
+    set_error(refusal);
     return GM_ERR_INVALID;
   }
   const bool shared = pre && pre->c;
-  if (shared && (pre->stride < n || (size_t)pre->W * pre->stride >= (size_t(1) << 31) || pre->narrow >= pre->W ||
-                 (size_t)pre->c * pre->W - pre->narrow < (size_t)C::FR_BITS + 1)) {
-    set_error("msm: precomputed point set does not cover this MSM");
-    return GM_ERR_INVALID;
-  }
-  const uint32_t c = shared ? pre->c
-                            : (ctx->msm_c_override ? (uint32_t)ctx->msm_c_override
-                                                   : (uint32_t)choose_window(n, plan.bits));
-  // ceil((bits+1)/c): the top signed digit never carries
-  const uint32_t W = shared ? pre->W : (uint32_t)(plan.bits + 1 + c - 1) / c;
-  plan.c = c;
-  plan.W = W;
-  plan.nb = 1u << (c - 1);
-  plan.Wred = shared ? 1 : W;
-  plan.total = plan.Wred * plan.nb;
-  plan.npts = shared ? (size_t)W * pre->stride : n;
-  const size_t M = (size_t)W * n;  // upper bound on the entries: zero digits are dropped
-  plan.M = M;
-  if (M >= (size_t(1) << 31)) {
-    set_error("msm: n * windows must be < 2^31");
-    return GM_ERR_INVALID;
-  }
-  // Sort geometry: ~2K entries per coarse bin for uniform digits (the final pass
-  // sorts a bin of up to S2_STAGE entries in LDS; the narrow top window's bins
-  // are ~2x fuller).  Pass-1 bins (b >> (F + G)) are coarsened by G until one
-  // pass-1 block (one window of S1 points in the plain layout) touches at most
-  // 512 of them (long write runs) and there are at most 8192; G > 0 adds the
-  // middle pass (msm_sort.hip).
-  SortGeom sg;
-  sg.T = plan.total;
-  sg.M = M;
-  sg.F = 4;
-  // A GLV plan's windows are full width (|k1|, |k2| < 0.87 * 2^127: no narrow top
-  // window) with twice the entries per bucket: ~4K-entry bins keep one pass-1
-  // block within 512 bins (no middle pass) and still fit S2_STAGE.
-  // The shared-bucket (precomputed) layout takes ~1.5K-entry bins: its 2^24 sort 3.78 -> 3.34 ms, 2^20 0.28 ->
-  // 0.19 ms against ~0.75K, while ~3K are slower again (profiles/r06v_shared_sort_bins_ab.txt); the plain
-  // layout's 2^24 sort is slower with ~2K bins than ~1K (3.29 -> 3.51 ms, r06u_sort_bins_ab.txt) and with ~0.5K
-  // (3.35 -> 3.83 ms, r06w_plain_sort_bins_ab.txt).
-  const double bin_entries = glv || shared ? 4096.0 : 2048.0;
-  while (sg.F < 13 && (double)M * std::ldexp(1.0, (int)sg.F + 1) <= bin_entries * sg.T) sg.F++;
-  auto bins = [&](uint32_t sh) { return (uint32_t)(((uint64_t)sg.T + (1ull << sh) - 1) >> sh); };
-  auto touched = [&](uint32_t sh) { return shared ? bins(sh) : std::max(1u, plan.nb >> sh); };
-  // GM_MSM_SORT_MING: minimum G (tests exercise the middle pass at small sizes)
-  const char* ming = getenv("GM_MSM_SORT_MING");
-  sg.G = ming ? (uint32_t)std::min(10, std::max(0, atoi(ming))) : 0u;
-  // (shared layout at 2^20: 8192 pass-1 bins with G = 0 measured 0.285 ms vs
-  // 0.315 with the middle pass -- its 109 MB of entries stay in the caches, which
-  // merge the short write runs; at 2^24, 1.6 GB, they do not: 2.4 ms per sort)
-  const uint32_t max_touched = (shared && M < (size_t(1) << 24)) ? 8192u : 512u;
-  while (sg.G < 10 && (touched(sg.F + sg.G) > max_touched || bins(sg.F + sg.G) > 8192)) sg.G++;
-  while (sg.G && sg.F + sg.G > 31) sg.G--;
-  sg.NC = bins(sg.F);
-  sg.NS = bins(sg.F + sg.G);
-  if (sg.NS > 8192) {
-    set_error("msm: too many buckets for the sort");
-    return GM_ERR_INVALID;
-  }
-  // 4-byte entries between the sort passes when the key bits below the pass-1
-  // bin, the sign and the largest point index fit (msm.hpp SortGeom);
-  // GM_MSM_SORT_WIDE=1 keeps 8 bytes (tests, A/B runs)
-  const char* wide = getenv("GM_MSM_SORT_WIDE");
-  sg.compact = !(wide && atoi(wide) > 0) && sort_compact_fits(sg.F, sg.G, plan.npts);
+  const uint32_t c = pg.c, W = pg.W;
+  const size_t M = pg.M;
+  const SortGeom& sg = pg.sg;
   int rc;
   DevBuf dig, keys_out, vals_out, offsets, scount;
   if ((rc = dig.alloc(arena, sizeof(uint32_t) * M)) || (keys && (rc = keys_out.alloc(arena, sizeof(uint32_t) * M))) ||
@@ -1001,12 +928,7 @@ int msm_plan(gm_ctx* ctx, Arena& arena, const void* scalars_dev, size_t n, const
   g.W = W;
   g.nb = plan.nb;
   g.shared_stride = shared ? (uint32_t)pre->stride : 0u;
-  g.wn = shared ? W - pre->narrow : W;
-  if (!shared && !glv) {
-    // plain layout: balance the windows (see DigitGeom)
-    const uint32_t narrow = c * W - (uint32_t)(plan.bits + 1);
-    if (narrow < W) g.wn = W - narrow;
-  }
+  g.wn = pg.wn;
   plan.wn = g.wn;
   g.F = sg.F + sg.G;  // the digits kernel counts pass-1 bins
   {
@@ -1064,19 +986,17 @@ int msm_reduce(gm_ctx* ctx, MsmTail& t) {
                          (const XYZZ<DF>*)t.buckets, (const uint32_t*)t.offsets, t.nb, t.L, t.nseg, t.Wr,
                          (XYZZ<DF>*)t.nodes_a);
   }
-  // LDS tree levels until one node per window
-  constexpr size_t SLOT_BUDGET = (96u << 10) / sizeof(XYZZ<DF>);
+  // LDS tree levels until one node per window (msm_tree_geom, msm.hpp)
+  MsmTreeGeom tg;
+  if (!msm_tree_geom(t.nseg, sizeof(XYZZ<DF>), tg)) {
+    set_error("msm: bucket reduction does not fit LDS");
+    return GM_ERR_INVALID;
+  }
   uint32_t m = t.nseg;
   XYZZ<DF>* cur = (XYZZ<DF>*)t.nodes_a;
   XYZZ<DF>* nxt = (XYZZ<DF>*)t.nodes_b;
-  while (m > 1) {
-    uint32_t lg = 0;
-    // largest power-of-two group with NT*Q slots in budget and <= 2 tasks per thread
-    while ((2u << lg) <= m && (size_t)(2u << lg) * Q <= SLOT_BUDGET && (1u << lg) * (Q + 1) <= 2 * BS_THREADS) lg++;
-    if (lg == 0) {
-      set_error("msm: bucket reduction does not fit LDS");
-      return GM_ERR_INVALID;
-    }
+  for (uint32_t lv = 0; lv < tg.levels; lv++) {
+    const uint32_t lg = tg.lg[lv];
     const uint32_t NT = 1u << lg;
     const uint32_t groups = m / NT;
     if constexpr (PairSel<DF>::ok) {
@@ -1165,17 +1085,8 @@ int msm_launch(gm_ctx* ctx, Arena& arena, const MsmPlan& plan, const void* point
   t.M = plan.M;
   t.keys = plan.keys;
   t.offsets = plan.offsets;
-  // level-1 segment length (buckets).  Measured at 2^20 (BN254 G1 / G2 /
-  // BLS12-377 G2 reduction ms): L = 1: 0.83 / 4.2 / 16.9, L = 2: 0.51 / 2.6 / 9.6,
-  // L = 4: 0.36 / 1.74 / 6.05 -- the LDS bit-sum trees cost more per add than the
-  // running sums.  So L grows (to 32) as long as k_msm_seg keeps >= 128K threads
-  // (two waves per SIMD): 4 for 2^20 plain, 16 for the one-window 2^21 buckets
-  // of a precomputed 2^24 key (segment lengths 4 / 8 re-measured in the pipelined
-  // loop, profiles/r05ai_segl_ab.txt).
-  uint32_t Lwant = 4;
-  while (Lwant < 32 && (size_t)t.Wr * t.nb / (2 * Lwant) >= (size_t(1) << 17)) Lwant *= 2;
-  t.L = t.nb >= Lwant ? Lwant : t.nb;
-  t.nseg = t.nb / t.L;
+  // level-1 segment length (buckets) and segments per window: msm_seg_geom, msm.hpp
+  msm_seg_geom(t.Wr, t.nb, t.L, t.nseg);
   // G2: entries per accumulation lane pair (slice length), 64; K % 4 == 0 (keys /
   // values arrive four entries per load), and the long-span bound FIX_SERIAL * K
   // stays above the fullest uniform bucket.  (128 for the Groth16 2^24 MSMs:

@@ -518,6 +518,86 @@ extern "C" int gm_test_msm_g2_keyless_plan(gm_ctx* ctx, int curve, const void* s
                            : g2_keyless_plan_t<CurveBLS12377>(ctx, scalars_dev, points_dev, n);
 }
 
+// The geometry of an MSM from the driver's own host functions (msm.hpp): no
+// context, no device call.  The allocations are msm_plan's offsets and
+// msm_launch's buckets and two node buffers.
+extern "C++" {
+template <class C, bool G2>
+static int msm_geometry_t(size_t n, int c_override, int layout, int curve, gm_test_msm_geom* out) {
+  using DF = typename GroupSel<C, G2>::DF;
+  MsmPrecomp pre;
+  bool glv = layout == GM_TGEOM_GLV;
+  if (layout == GM_TGEOM_DEFAULT) glv = msm_glv_on(nullptr, G2, n);
+  if (layout == GM_TGEOM_PRECOMP) {
+    int c = 0, W = 0;
+    if (int rc = gm_precompute_layout(curve, n, c_override, &c, &W)) return rc;
+    pre.c = (uint32_t)c;
+    pre.W = (uint32_t)W;
+    pre.narrow = precomp_narrow(pre.c, pre.W, C::FR_BITS);
+    pre.stride = n;
+  }
+  MsmPlanGeom pg;
+  if (const char* refusal = msm_plan_geom(n, C::FR_BITS, glv, pre.c ? &pre : nullptr, c_override, pg)) {
+    set_error(refusal);
+    return GM_ERR_INVALID;
+  }
+  gm_test_msm_geom& o = *out;
+  memset(&o, 0, sizeof(o));
+  o.c = pg.c;
+  o.W = pg.W;
+  o.wn = pg.wn;
+  o.narrow = pg.W - pg.wn;
+  o.Wred = pg.Wred;
+  o.nb = pg.nb;
+  o.total = pg.total;
+  o.glv = glv;
+  o.shared = pre.c != 0;
+  o.bits = (uint32_t)pg.bits;
+  o.F = pg.sg.F;
+  o.G = pg.sg.G;
+  o.NC = pg.sg.NC;
+  o.NS = pg.sg.NS;
+  o.compact = pg.sg.compact;
+  o.piece_len = msm_piece_len(nullptr, pg.M);
+  o.n = pg.n;
+  o.M = pg.M;
+  o.npts = pg.npts;
+  msm_seg_geom(pg.Wred, pg.nb, o.L, o.nseg);
+  MsmTreeGeom tg;
+  if (!msm_tree_geom(o.nseg, sizeof(XYZZ<DF>), tg)) {
+    set_error("msm: bucket reduction does not fit LDS");
+    return GM_ERR_INVALID;
+  }
+  static_assert(GM_TGEOM_MAX_LEVELS == MsmTreeGeom::MAX_LEVELS, "report and driver hold the same levels");
+  o.levels = tg.levels;
+  for (uint32_t i = 0; i < tg.levels; i++) o.lg[i] = tg.lg[i];
+  o.Q = tg.Q;
+  o.xyzz_bytes = (uint32_t)sizeof(XYZZ<DF>);
+  o.bucket_bytes = (uint64_t)sizeof(XYZZ<DF>) * pg.total;
+  o.node_bytes = 2 * (uint64_t)sizeof(XYZZ<DF>) * 2 * pg.Wred * o.nseg;
+  o.offset_bytes = (uint64_t)sizeof(uint32_t) * ((uint64_t)pg.total + 1);
+  return GM_OK;
+}
+}
+
+extern "C" int gm_test_msm_geometry(int curve, int g2, size_t n, int c_override, int layout, gm_test_msm_geom* out) {
+  if (!out || n == 0 || layout < GM_TGEOM_PLAIN || layout > GM_TGEOM_DEFAULT ||
+      (curve != GM_BN254 && curve != GM_BLS12_377)) {
+    set_error("msm geometry: bad curve, size or layout");
+    return GM_ERR_INVALID;
+  }
+  // the window range of gm_set_msm_window (the precomputed range is checked by gm_precompute_layout)
+  if (c_override != 0 && (c_override < 2 || c_override > 24)) {
+    set_error("msm geometry: window must be 0 (auto) or in [2, 24]");
+    return GM_ERR_INVALID;
+  }
+  if (curve == GM_BN254)
+    return g2 ? msm_geometry_t<CurveBN254, true>(n, c_override, layout, curve, out)
+              : msm_geometry_t<CurveBN254, false>(n, c_override, layout, curve, out);
+  return g2 ? msm_geometry_t<CurveBLS12377, true>(n, c_override, layout, curve, out)
+            : msm_geometry_t<CurveBLS12377, false>(n, c_override, layout, curve, out);
+}
+
 /* The solver-side cost of staging the reference benchmark circuit's level shape
  * (backend/groth16/groth16_test.go:120-156: a chain of squarings; the solver runs
  * it as one one-instruction level after another, constraint/bn254/solver.go:

@@ -67,7 +67,8 @@ SYMBOLS = [
 ]
 # test-only library (include/gnark_mi355x_testhooks.h, libgnark_mi355x_testhooks.so)
 TEST_SYMBOLS = ["gm_test_field_op", "gm_test_point_op", "gm_test_stage_replay_chain",
-                "gm_test_msm_g2_keyless_plan", "gm_test_field_raw_op", "gm_test_point_raw_op"]
+                "gm_test_msm_g2_keyless_plan", "gm_test_field_raw_op", "gm_test_point_raw_op",
+                "gm_test_msm_geometry"]
 TESTHOOKS_PATH = os.path.join(os.path.dirname(LIB_PATH), "libgnark_mi355x_testhooks.so")
 
 
@@ -175,6 +176,20 @@ class _G16SetupOut(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in G16_SETUP_OUT_FIELDS]
 
 
+# gm_test_msm_geometry layouts (include/gnark_mi355x_testhooks.h)
+TGEOM_PLAIN, TGEOM_GLV, TGEOM_PRECOMP, TGEOM_DEFAULT = 0, 1, 2, 3
+TGEOM_MAX_LEVELS = 24
+
+
+class _MsmGeom(ctypes.Structure):
+    """gm_test_msm_geom (include/gnark_mi355x_testhooks.h)."""
+    _fields_ = ([(k, ctypes.c_uint32) for k in ("c", "W", "wn", "narrow", "Wred", "nb", "total", "glv", "shared",
+                                                "bits", "F", "G", "NC", "NS", "compact", "piece_len", "L", "nseg",
+                                                "levels")]
+                + [("lg", ctypes.c_uint32 * TGEOM_MAX_LEVELS), ("Q", ctypes.c_uint32), ("xyzz_bytes", ctypes.c_uint32)]
+                + [(k, ctypes.c_uint64) for k in ("n", "M", "npts", "bucket_bytes", "node_bytes", "offset_bytes")])
+
+
 _lib = None
 _testhooks = None
 
@@ -197,6 +212,7 @@ def load_testhooks(path: str = None):
     T.gm_test_msm_g2_keyless_plan.argtypes = [vp, i, vp, vp, sz]
     T.gm_test_field_raw_op.argtypes = [vp, i, i, i, i, vp, vp, vp, vp, vp, sz]
     T.gm_test_point_raw_op.argtypes = [vp, i, i, i, i, vp, vp, vp, vp, sz]
+    T.gm_test_msm_geometry.argtypes = [i, i, sz, i, i, ctypes.POINTER(_MsmGeom)]
     _testhooks = T
     return T
 
@@ -373,6 +389,18 @@ def jac_to_affine(curve, g2: bool, p: bytes) -> bytes:
     a = _buf(p)
     _check(load_library().gm_jac_to_affine(curve_id(curve), int(g2), _p(a), _p(out)))
     return out.tobytes()
+
+
+def msm_geometry(curve, g2: bool, n: int, c: int = 0, layout: int = TGEOM_PLAIN) -> dict:
+    """gm_test_msm_geometry: what an MSM of n scalars derives from its sizes
+    (windows, sort bins, segment length, tree levels, allocations), from the
+    driver's own host functions.  Needs no device.  Raises GmError where the plan
+    refuses the MSM."""
+    g = _MsmGeom()
+    _check(load_testhooks().gm_test_msm_geometry(curve_id(curve), int(g2), n, c, layout, ctypes.byref(g)))
+    out = {k: int(getattr(g, k)) for k, _ in _MsmGeom._fields_ if k != "lg"}
+    out["lg"] = tuple(int(g.lg[i]) for i in range(g.levels))
+    return out
 
 
 class DeviceBuffer:

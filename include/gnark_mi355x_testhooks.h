@@ -91,6 +91,37 @@ int gm_test_stage_replay_chain(gm_g16_stage* st, const void* wires, size_t nb_in
  * holds n G2 points; nothing reads them when the launch refuses. */
 int gm_test_msm_g2_keyless_plan(gm_ctx* ctx, int curve, const void* scalars_dev, const void* points_dev, size_t n);
 
+/* Host-only report of the geometry an MSM of n scalars derives from its sizes:
+ * the functions the driver itself calls (msm.hpp msm_plan_geom, msm_seg_geom,
+ * msm_tree_geom), with no context and no device.  c_override is the window as
+ * gm_set_msm_window takes it (0: the cost model); for the precomputed layout it
+ * is the window of the prepared set of n points (0: the shared-bucket cost
+ * model, as gm_precompute_layout reports it).  GM_ERR_INVALID with
+ * gm_last_error where the plan would refuse the MSM. */
+#define GM_TGEOM_PLAIN 0    /* gnark-layout points, GLV split off */
+#define GM_TGEOM_GLV 1      /* gnark-layout points, GLV split on */
+#define GM_TGEOM_PRECOMP 2  /* precomputed set, one shared bucket set */
+#define GM_TGEOM_DEFAULT 3  /* gnark-layout points, GLV by the size rule */
+#define GM_TGEOM_MAX_LEVELS 24
+typedef struct gm_test_msm_geom {
+  /* plan */
+  uint32_t c, W;            /* window bits, windows */
+  uint32_t wn, narrow;      /* first narrow (c - 1 bit) window; W - wn */
+  uint32_t Wred, nb, total; /* windows reduced separately; buckets per window; Wred * nb */
+  uint32_t glv, shared;     /* the layout taken (GM_TGEOM_DEFAULT resolves glv) */
+  uint32_t bits;            /* scalar bits the digits cover */
+  uint32_t F, G, NC, NS, compact; /* the sort's bins and entry width */
+  uint32_t piece_len;       /* G1 piece length by the size rule */
+  /* launch and reduction */
+  uint32_t L, nseg;         /* level-1 segment length and segments per window */
+  uint32_t levels, lg[GM_TGEOM_MAX_LEVELS]; /* LDS tree levels, log2 of each group */
+  uint32_t Q;               /* points per exported node */
+  uint32_t xyzz_bytes;      /* bytes of one bucket of this group */
+  uint64_t n, M, npts;      /* (virtual) points, entry bound, addressable points */
+  uint64_t bucket_bytes, node_bytes, offset_bytes; /* what the launch and the plan allocate for them */
+} gm_test_msm_geom;
+int gm_test_msm_geometry(int curve, int g2, size_t n, int c_override, int layout, gm_test_msm_geom* out);
+
 #ifdef __cplusplus
 }
 #endif
