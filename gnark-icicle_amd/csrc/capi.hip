@@ -41,7 +41,7 @@ GM_DEV uint64_t splitmix64(uint64_t& x) {
 }
 
 // n Montgomery (gnark-layout) scalars: random canonical value below 2^BITS,
-// reduced once (2^BITS < 2r for both scalar fields), then x*Rg.
+// reduced once (2^BITS < 2r for every scalar field), then x*Rg.
 template <class Fr>
 __global__ void k_random_scalars(uint32_t* out, size_t n, uint64_t seed) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -112,15 +112,35 @@ static int msm_to_host(gm_ctx* ctx, const void* sc, const void* pts, size_t n, v
   return GM_OK;
 }
 
-static int check_curve(int curve) {
-  if (curve != GM_BN254 && curve != GM_BLS12_377) {
+int check_curve(int curve, CurveCaps caps, const char* entry) {
+  if (curve < 0 || curve >= CURVE_COUNT) {
     set_error("unknown curve id");
     return GM_ERR_INVALID;
+  }
+  if (curve == CurveBLS12381::id && caps != CURVES_ALL) {
+    set_error(std::string(entry) + ": not built for " + curve_name(curve) + " (curve id " + std::to_string(curve) +
+              ")");
+    return GM_ERR_UNSUPPORTED;
   }
   return GM_OK;
 }
 
-size_t fp_bytes(int curve) { return curve == GM_BN254 ? 32 : 48; }
+size_t fp_bytes(int curve) {
+  static constexpr size_t t[CURVE_COUNT] = {sizeof(CurveBN254::HG1F), sizeof(CurveBLS12377::HG1F),
+                                            sizeof(CurveBLS12381::HG1F)};
+  return curve >= 0 && curve < CURVE_COUNT ? t[curve] : 0;
+}
+
+// bytes of one device-internal point of a prepared set (0 for an unknown id)
+static size_t internal_point_bytes(int curve, int g2) {
+  return with_curve(
+      curve,
+      [&](auto tag_) {
+        using C = typename decltype(tag_)::type;
+        return g2 ? msm_internal_point_bytes<C, true>() : msm_internal_point_bytes<C, false>();
+      },
+      (size_t)0);
+}
 
 void orphan_pending_msms(gm_ctx* ctx);  // below gm_msm_pending
 
@@ -366,7 +386,7 @@ int gm_copy_to_device(gm_ctx* ctx, const void* host, size_t bytes, void** dev_ou
 }
 int gm_copy_points_to_device(gm_ctx* ctx, int curve, int g2, const void* host_points, size_t n,
                              void** dev_out) {
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_copy_points_to_device")) return rc;
   return gm_copy_to_device(ctx, host_points, n * fp_bytes(curve) * (g2 ? 4 : 2), dev_out);
 }
 
@@ -374,16 +394,11 @@ int gm_copy_points_to_device(gm_ctx* ctx, int curve, int g2, const void* host_po
 int gm_msm(gm_ctx* ctx, int curve, int g2, const void* scalars_dev, const void* points_dev,
            size_t n, void* out_jac, void* out_affine) {
   if (!ctx) return GM_ERR_INVALID;
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_msm")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  int rc;
-  if (curve == GM_BN254)
-    rc = g2 ? msm_to_host<CurveBN254, true>(ctx, scalars_dev, points_dev, n, out_jac, out_affine)
-            : msm_to_host<CurveBN254, false>(ctx, scalars_dev, points_dev, n, out_jac, out_affine);
-  else
-    rc = g2 ? msm_to_host<CurveBLS12377, true>(ctx, scalars_dev, points_dev, n, out_jac, out_affine)
-            : msm_to_host<CurveBLS12377, false>(ctx, scalars_dev, points_dev, n, out_jac, out_affine);
+  const int rc = GM_CURVE(curve, g2 ? msm_to_host<C, true>(ctx, scalars_dev, points_dev, n, out_jac, out_affine)
+                                    : msm_to_host<C, false>(ctx, scalars_dev, points_dev, n, out_jac, out_affine));
   prof_collect(ctx);
   return rc;
 }
@@ -410,7 +425,11 @@ bool gm::msm_glv_on(const gm_ctx* ctx, bool g2, size_t n) {
   // 2^20 it halves the bucket reduction (BN254 G1 2.26 -> 2.14 ms, G2 7.65 ->
   // 6.51 ms); at 2^22 (BLS12-377) the reduction is a small share while the 2n
   // virtual points double the gathered point set (G1 14.2 -> 15.8 ms, G2 56.6
-  // -> 62.1 ms).  gm_set_msm_glv overrides it per context.
+  // -> 62.1 ms).  BLS12-381 (curve id 2) was measured on its own, not inherited
+  // (profiles/bls12381_timing.json, medians of five): 2^20 G1 4.23 -> 3.84 ms, G2
+  // 12.72 -> 11.31 ms with GLV; 2^22 G1 13.32 -> 13.78 ms, G2 38.22 -> 37.89 ms
+  // (inside each other's spread): the same threshold holds for it, so the
+  // default takes no curve.  gm_set_msm_glv overrides it per context.
   if (n > (size_t(1) << 21)) return false;
   return true;
 }
@@ -464,7 +483,7 @@ int msm_wait_t(gm_msm_pending* p, void* out_jac, void* out_aff) {
 int gm::msm_async_queue(gm_ctx* ctx, int curve, int g2, const void* scalars_dev, const void* points_dev, size_t n,
                         bool prepared, gm_msm_pending** out) {
   if (!ctx || !out) return GM_ERR_INVALID;
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_msm_async")) return rc;
   // no CtxLock: nothing is queued on ctx->stream here (gm_ctx::pending_reads)
   std::lock_guard<std::recursive_mutex> g(ctx->mu);
   GM_HIP(hipSetDevice(ctx->device));
@@ -526,12 +545,9 @@ int gm::msm_async_queue(gm_ctx* ctx, int curve, int g2, const void* scalars_dev,
       Arena& a = *p->slot.a;
       const void* sc = scalars_dev;
       const void* pt = points_dev;
-      if (curve == GM_BN254)
-        rc = g2 ? msm_device_launch<CurveBN254, true>(ctx, a, sc, pt, n, prepared, nullptr, p->tail, inputs_read)
-                : msm_device_launch<CurveBN254, false>(ctx, a, sc, pt, n, prepared, nullptr, p->tail, inputs_read);
-      else
-        rc = g2 ? msm_device_launch<CurveBLS12377, true>(ctx, a, sc, pt, n, prepared, nullptr, p->tail, inputs_read)
-                : msm_device_launch<CurveBLS12377, false>(ctx, a, sc, pt, n, prepared, nullptr, p->tail, inputs_read);
+      rc = GM_CURVE(curve,
+                    g2 ? msm_device_launch<C, true>(ctx, a, sc, pt, n, prepared, nullptr, p->tail, inputs_read)
+                       : msm_device_launch<C, false>(ctx, a, sc, pt, n, prepared, nullptr, p->tail, inputs_read));
     }
   }
   if (inputs_read && rc) hipEventDestroy(inputs_read);
@@ -574,13 +590,9 @@ int gm_msm_wait(gm_msm_pending* p, void* out_jac, void* out_affine) {
       ++it;
     }
   GM_HIP(hipSetDevice(ctx->device));
-  int rc;
   StreamSwap sw(ctx, p->st);  // a long-span redo runs on the MSM's own stream
-  if (p->curve == GM_BN254)
-    rc = p->g2 ? msm_wait_t<CurveBN254, true>(p, out_jac, out_affine) : msm_wait_t<CurveBN254, false>(p, out_jac, out_affine);
-  else
-    rc = p->g2 ? msm_wait_t<CurveBLS12377, true>(p, out_jac, out_affine)
-               : msm_wait_t<CurveBLS12377, false>(p, out_jac, out_affine);
+  const int rc = GM_CURVE(p->curve, p->g2 ? msm_wait_t<C, true>(p, out_jac, out_affine)
+                                          : msm_wait_t<C, false>(p, out_jac, out_affine));
   prof_collect(ctx);
   delete p;
   return rc;
@@ -589,6 +601,7 @@ int gm_msm_wait(gm_msm_pending* p, void* out_jac, void* out_affine) {
 int gm_msm_host_scalars(gm_ctx* ctx, int curve, int g2, const void* scalars_host,
                         const void* points_dev, size_t n, void* out_jac, void* out_affine) {
   if (!ctx || (n && !scalars_host)) return GM_ERR_INVALID;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_msm_host_scalars")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
   Arena arena(ctx);
@@ -601,14 +614,11 @@ int gm_msm_host_scalars(gm_ctx* ctx, int curve, int g2, const void* scalars_host
 
 int gm_points_upload(gm_ctx* ctx, int curve, int g2, const void* host_points, size_t n, void** out) {
   if (!ctx || !out) return GM_ERR_INVALID;
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_points_upload")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
   const size_t gb = fp_bytes(curve) * (g2 ? 4 : 2) * n;
-  const size_t ib = n * (curve == GM_BN254 ? (g2 ? msm_internal_point_bytes<CurveBN254, true>()
-                                                 : msm_internal_point_bytes<CurveBN254, false>())
-                                           : (g2 ? msm_internal_point_bytes<CurveBLS12377, true>()
-                                                 : msm_internal_point_bytes<CurveBLS12377, false>()));
+  const size_t ib = n * internal_point_bytes(curve, g2);
   Arena arena(ctx);
   DevBuf tmp;
   int rc;
@@ -619,12 +629,8 @@ int gm_points_upload(gm_ctx* ctx, int curve, int g2, const void* host_points, si
     return GM_ERR_OOM;
   }
   GM_HIP(hipMemcpyAsync(tmp.p, host_points, gb, hipMemcpyHostToDevice, ctx->stream));
-  if (curve == GM_BN254)
-    rc = g2 ? msm_prepare_points<CurveBN254, true>(ctx, tmp.p, n, *out)
-            : msm_prepare_points<CurveBN254, false>(ctx, tmp.p, n, *out);
-  else
-    rc = g2 ? msm_prepare_points<CurveBLS12377, true>(ctx, tmp.p, n, *out)
-            : msm_prepare_points<CurveBLS12377, false>(ctx, tmp.p, n, *out);
+  rc = GM_CURVE(curve, g2 ? msm_prepare_points<C, true>(ctx, tmp.p, n, *out)
+                          : msm_prepare_points<C, false>(ctx, tmp.p, n, *out));
   if (rc) return rc;
   GM_HIP(hipStreamSynchronize(ctx->stream));
   return GM_OK;
@@ -650,23 +656,18 @@ static int msm_prepared_t(gm_ctx* ctx, const void* sc, const void* pts, size_t n
 int gm_msm_prepared(gm_ctx* ctx, int curve, int g2, const void* scalars_dev, const void* prepared, size_t n,
                     void* out_jac, void* out_affine) {
   if (!ctx) return GM_ERR_INVALID;
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_msm_prepared")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  int rc;
-  if (curve == GM_BN254)
-    rc = g2 ? msm_prepared_t<CurveBN254, true>(ctx, scalars_dev, prepared, n, out_jac, out_affine)
-            : msm_prepared_t<CurveBN254, false>(ctx, scalars_dev, prepared, n, out_jac, out_affine);
-  else
-    rc = g2 ? msm_prepared_t<CurveBLS12377, true>(ctx, scalars_dev, prepared, n, out_jac, out_affine)
-            : msm_prepared_t<CurveBLS12377, false>(ctx, scalars_dev, prepared, n, out_jac, out_affine);
+  const int rc = GM_CURVE(curve, g2 ? msm_prepared_t<C, true>(ctx, scalars_dev, prepared, n, out_jac, out_affine)
+                                    : msm_prepared_t<C, false>(ctx, scalars_dev, prepared, n, out_jac, out_affine));
   prof_collect(ctx);
   return rc;
 }
 
 // ---- fixed-base precomputed point sets -------------------------------------------
 static int make_precomp(int curve, size_t n, int window, MsmPrecomp* out) {
-  const int bits = curve == GM_BN254 ? CurveBN254::FR_BITS : CurveBLS12377::FR_BITS;
+  const int bits = fr_bits(curve);
   if (window == 0) {
     *out = msm_choose_precomp(n, bits);
     return GM_OK;
@@ -683,7 +684,7 @@ static int make_precomp(int curve, size_t n, int window, MsmPrecomp* out) {
 }
 
 int gm_precompute_layout(int curve, size_t n, int window, int* c_out, int* copies_out) {
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_precompute_layout")) return rc;
   MsmPrecomp p;
   if (int rc = make_precomp(curve, n, window, &p)) return rc;
   if (c_out) *c_out = (int)p.c;
@@ -694,7 +695,7 @@ int gm_precompute_layout(int curve, size_t n, int window, int* c_out, int* copie
 int gm_points_upload_precomputed(gm_ctx* ctx, int curve, int g2, const void* host_points, size_t n, int window,
                                  void** out) {
   if (!ctx || !out) return GM_ERR_INVALID;
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_points_upload_precomputed")) return rc;
   MsmPrecomp pre;
   if (int rc = make_precomp(curve, n, window, &pre)) return rc;
   if ((size_t)pre.W * n >= (size_t(1) << 31)) {
@@ -704,11 +705,7 @@ int gm_points_upload_precomputed(gm_ctx* ctx, int curve, int g2, const void* hos
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
   const size_t gb = fp_bytes(curve) * (g2 ? 4 : 2) * n;
-  const size_t ib = (size_t)pre.W * n *
-                    (curve == GM_BN254 ? (g2 ? msm_internal_point_bytes<CurveBN254, true>()
-                                             : msm_internal_point_bytes<CurveBN254, false>())
-                                       : (g2 ? msm_internal_point_bytes<CurveBLS12377, true>()
-                                             : msm_internal_point_bytes<CurveBLS12377, false>()));
+  const size_t ib = (size_t)pre.W * n * internal_point_bytes(curve, g2);
   Arena arena(ctx);
   DevBuf tmp;
   int rc;
@@ -719,12 +716,8 @@ int gm_points_upload_precomputed(gm_ctx* ctx, int curve, int g2, const void* hos
     return GM_ERR_OOM;
   }
   if (gb) GM_HIP(hipMemcpyAsync(tmp.p, host_points, gb, hipMemcpyHostToDevice, ctx->stream));
-  if (curve == GM_BN254)
-    rc = g2 ? msm_precompute_points<CurveBN254, true>(ctx, tmp.p, n, pre, *out)
-            : msm_precompute_points<CurveBN254, false>(ctx, tmp.p, n, pre, *out);
-  else
-    rc = g2 ? msm_precompute_points<CurveBLS12377, true>(ctx, tmp.p, n, pre, *out)
-            : msm_precompute_points<CurveBLS12377, false>(ctx, tmp.p, n, pre, *out);
+  rc = GM_CURVE(curve, g2 ? msm_precompute_points<C, true>(ctx, tmp.p, n, pre, *out)
+                          : msm_precompute_points<C, false>(ctx, tmp.p, n, pre, *out));
   if (rc) return rc;
   GM_HIP(hipStreamSynchronize(ctx->stream));
   return GM_OK;
@@ -733,7 +726,7 @@ int gm_points_upload_precomputed(gm_ctx* ctx, int curve, int g2, const void* hos
 int gm_msm_precomputed(gm_ctx* ctx, int curve, int g2, const void* scalars_dev, const void* prepared,
                        size_t prepared_n, int window, size_t n, void* out_jac, void* out_affine) {
   if (!ctx) return GM_ERR_INVALID;
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_msm_precomputed")) return rc;
   if (n > prepared_n) {
     set_error("msm_precomputed: n exceeds the prepared point count");
     return GM_ERR_INVALID;
@@ -742,13 +735,9 @@ int gm_msm_precomputed(gm_ctx* ctx, int curve, int g2, const void* scalars_dev, 
   if (int rc = make_precomp(curve, prepared_n, window, &pre)) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  int rc;
-  if (curve == GM_BN254)
-    rc = g2 ? msm_prepared_t<CurveBN254, true>(ctx, scalars_dev, prepared, n, out_jac, out_affine, &pre)
-            : msm_prepared_t<CurveBN254, false>(ctx, scalars_dev, prepared, n, out_jac, out_affine, &pre);
-  else
-    rc = g2 ? msm_prepared_t<CurveBLS12377, true>(ctx, scalars_dev, prepared, n, out_jac, out_affine, &pre)
-            : msm_prepared_t<CurveBLS12377, false>(ctx, scalars_dev, prepared, n, out_jac, out_affine, &pre);
+  const int rc =
+      GM_CURVE(curve, g2 ? msm_prepared_t<C, true>(ctx, scalars_dev, prepared, n, out_jac, out_affine, &pre)
+                         : msm_prepared_t<C, false>(ctx, scalars_dev, prepared, n, out_jac, out_affine, &pre));
   prof_collect(ctx);
   return rc;
 }
@@ -756,6 +745,7 @@ int gm_msm_precomputed(gm_ctx* ctx, int curve, int g2, const void* scalars_dev, 
 int gm_kzg_commit(gm_ctx* ctx, int curve, const void* srs, size_t srs_len, const void* coeffs_host, size_t n,
                   void* digest_affine) {
   if (!ctx || !digest_affine) return GM_ERR_INVALID;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_kzg_commit")) return rc;
   if (n > srs_len) {
     set_error("kzg commit: polynomial larger than the SRS");
     return GM_ERR_INVALID;
@@ -775,11 +765,10 @@ int gm_kzg_commit(gm_ctx* ctx, int curve, const void* srs, size_t srs_len, const
 int gm_kzg_eval(gm_ctx* ctx, int curve, const void* const* polys_dev, const size_t* lens, size_t k,
                 const void* z_host, void* values_host) {
   if (!ctx || !z_host || !values_host) return GM_ERR_INVALID;
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_kzg_eval")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  const int rc = curve == GM_BN254 ? poly_eval_device<CurveBN254>(ctx, polys_dev, lens, k, z_host, values_host)
-                                   : poly_eval_device<CurveBLS12377>(ctx, polys_dev, lens, k, z_host, values_host);
+  const int rc = GM_CURVE(curve, poly_eval_device<C>(ctx, polys_dev, lens, k, z_host, values_host));
   prof_collect(ctx);
   return rc;
 }
@@ -787,11 +776,10 @@ int gm_kzg_eval(gm_ctx* ctx, int curve, const void* const* polys_dev, const size
 int gm_poly_div_linear(gm_ctx* ctx, int curve, const void* f_dev, size_t m, const void* z_host, void* q_dev,
                        void* value_host) {
   if (!ctx || !z_host || !value_host) return GM_ERR_INVALID;
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_poly_div_linear")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  const int rc = curve == GM_BN254 ? poly_div_linear_device<CurveBN254>(ctx, f_dev, m, z_host, q_dev, value_host)
-                                   : poly_div_linear_device<CurveBLS12377>(ctx, f_dev, m, z_host, q_dev, value_host);
+  const int rc = GM_CURVE(curve, poly_div_linear_device<C>(ctx, f_dev, m, z_host, q_dev, value_host));
   prof_collect(ctx);
   return rc;
 }
@@ -799,11 +787,10 @@ int gm_poly_div_linear(gm_ctx* ctx, int curve, const void* f_dev, size_t m, cons
 int gm_poly_fold(gm_ctx* ctx, int curve, const void* const* polys_dev, const size_t* lens, size_t k,
                  const void* gamma_host, void* out_dev) {
   if (!ctx || !gamma_host) return GM_ERR_INVALID;
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_poly_fold")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  const int rc = curve == GM_BN254 ? poly_fold_device<CurveBN254>(ctx, polys_dev, lens, k, gamma_host, out_dev)
-                                   : poly_fold_device<CurveBLS12377>(ctx, polys_dev, lens, k, gamma_host, out_dev);
+  const int rc = GM_CURVE(curve, poly_fold_device<C>(ctx, polys_dev, lens, k, gamma_host, out_dev));
   prof_collect(ctx);
   return rc;
 }
@@ -822,8 +809,7 @@ static int kzg_open_resident(gm_ctx* ctx, int curve, const void* srs, size_t srs
   int rc;
   if ((rc = q.alloc(arena, 32 * (m - 1)))) return rc;
   ProfScope ps(ctx, "kzg_open_call");  // division + MSM (collected by the next profile read)
-  rc = curve == GM_BN254 ? poly_div_linear_device<CurveBN254>(ctx, f_dev, m, z_host, q.p, value_host)
-                         : poly_div_linear_device<CurveBLS12377>(ctx, f_dev, m, z_host, q.p, value_host);
+  rc = GM_CURVE(curve, poly_div_linear_device<C>(ctx, f_dev, m, z_host, q.p, value_host));
   if (rc) return rc;
   if (m == 1) {
     memset(h_affine, 0, 2 * fp_bytes(curve));
@@ -835,7 +821,7 @@ static int kzg_open_resident(gm_ctx* ctx, int curve, const void* srs, size_t srs
 int gm_kzg_open(gm_ctx* ctx, int curve, const void* srs, size_t srs_len, const void* f_dev, size_t m,
                 const void* z_host, void* claimed_host, void* h_affine) {
   if (!ctx || !z_host || !claimed_host || !h_affine) return GM_ERR_INVALID;
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_kzg_open")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
   // the kernels' profile records are drained inside; the whole-call record closes
@@ -847,7 +833,7 @@ int gm_kzg_batch_open(gm_ctx* ctx, int curve, const void* srs, size_t srs_len, c
                       const size_t* lens, size_t k, const void* z_host, const void* gamma_host,
                       void* folded_value_host, void* h_affine) {
   if (!ctx || !z_host || !gamma_host || !h_affine) return GM_ERR_INVALID;
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_kzg_batch_open")) return rc;
   if (!polys_dev || !lens || k == 0) {
     set_error("kzg batch open: no polynomials");
     return GM_ERR_INVALID;
@@ -864,8 +850,7 @@ int gm_kzg_batch_open(gm_ctx* ctx, int curve, const void* srs, size_t srs_len, c
   DevBuf folded;
   int rc;
   if ((rc = folded.alloc(arena, 32 * m))) return rc;
-  rc = curve == GM_BN254 ? poly_fold_device<CurveBN254>(ctx, polys_dev, lens, k, gamma_host, folded.p)
-                         : poly_fold_device<CurveBLS12377>(ctx, polys_dev, lens, k, gamma_host, folded.p);
+  rc = GM_CURVE(curve, poly_fold_device<C>(ctx, polys_dev, lens, k, gamma_host, folded.p));
   uint64_t value[4];
   if (!rc) rc = kzg_open_resident(ctx, curve, srs, srs_len, folded.p, m, z_host, value, h_affine);
   if (!rc && folded_value_host) memcpy(folded_value_host, value, sizeof(value));
@@ -874,15 +859,14 @@ int gm_kzg_batch_open(gm_ctx* ctx, int curve, const void* srs, size_t srs_len, c
 
 // ---- PLONK quotient on resident polynomials (plonk.hip) -----------------------------
 int gm_plonk_quotient(gm_ctx* ctx, int curve, const gm_plonk_quotient_in* in, void* h_dev) {
+  if (int rc = check_curve(curve, CURVES_01, "gm_plonk_quotient")) return rc;
   if (!ctx || !in || !h_dev) return GM_ERR_INVALID;
-  if (int rc = check_curve(curve)) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
   int rc;
   {
     ProfScope ps(ctx, "plonk_quotient_call");
-    rc = curve == GM_BN254 ? plonk_quotient_device<CurveBN254>(ctx, in, h_dev)
-                           : plonk_quotient_device<CurveBLS12377>(ctx, in, h_dev);
+    rc = GM_CURVE01(curve, plonk_quotient_device<C>(ctx, in, h_dev));
   }
   // also after a refusal part-way: nothing queued may outlive the call's workspace
   GM_HIP(hipStreamSynchronize(ctx->stream));
@@ -893,15 +877,14 @@ int gm_plonk_quotient(gm_ctx* ctx, int curve, const gm_plonk_quotient_in* in, vo
 // ---- PLONK permutation polynomial Z on resident wires (plonk_perm.hip) --------------
 int gm_plonk_perm_z(gm_ctx* ctx, int curve, const gm_plonk_perm_in* in, void* z_lagrange_dev,
                     void* z_canonical_dev) {
+  if (int rc = check_curve(curve, CURVES_01, "gm_plonk_perm_z")) return rc;
   if (!ctx || !in || !z_lagrange_dev) return GM_ERR_INVALID;
-  if (int rc = check_curve(curve)) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
   int rc;
   {
     ProfScope ps(ctx, "plonk_perm_z_call");
-    rc = curve == GM_BN254 ? plonk_perm_z_device<CurveBN254>(ctx, in, z_lagrange_dev, z_canonical_dev)
-                           : plonk_perm_z_device<CurveBLS12377>(ctx, in, z_lagrange_dev, z_canonical_dev);
+    rc = GM_CURVE01(curve, plonk_perm_z_device<C>(ctx, in, z_lagrange_dev, z_canonical_dev));
   }
   // also after a refusal part-way: nothing queued may outlive the call's workspace
   GM_HIP(hipStreamSynchronize(ctx->stream));
@@ -911,15 +894,14 @@ int gm_plonk_perm_z(gm_ctx* ctx, int curve, const gm_plonk_perm_in* in, void* z_
 
 // ---- PLONK linearized polynomial on resident buffers (plonk_lin.hip) ----------------
 int gm_plonk_linearize(gm_ctx* ctx, int curve, const gm_plonk_linearize_in* in, const gm_plonk_linearize_out* out) {
+  if (int rc = check_curve(curve, CURVES_01, "gm_plonk_linearize")) return rc;
   if (!ctx || !in || !out) return GM_ERR_INVALID;
-  if (int rc = check_curve(curve)) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
   int rc;
   {
     ProfScope ps(ctx, "plonk_linearize_call");
-    rc = curve == GM_BN254 ? plonk_linearize_device<CurveBN254>(ctx, in, out)
-                           : plonk_linearize_device<CurveBLS12377>(ctx, in, out);
+    rc = GM_CURVE01(curve, plonk_linearize_device<C>(ctx, in, out));
   }
   // also after a refusal part-way: nothing queued may outlive the call's workspace
   GM_HIP(hipStreamSynchronize(ctx->stream));
@@ -934,8 +916,8 @@ static int refuse_null(const char* what) {
 }
 
 int gm_plonk_pk_upload(gm_ctx* ctx, int curve, const gm_plonk_pk_host* pk, unsigned flags, gm_plonk_pk** out) {
+  if (int rc = check_curve(curve, CURVES_01, "gm_plonk_pk_upload")) return rc;
   if (!ctx || !pk || !out) return refuse_null("plonk pk upload");
-  if (int rc = check_curve(curve)) return rc;
   return plonk_pk_upload(ctx, curve, pk, flags, out);
 }
 
@@ -1078,8 +1060,8 @@ int gm_plonk_session_bsb22_sparse(gm_plonk_session* s, size_t j, const uint32_t*
 
 // ---- PLONK setup on the device (plonk_setup.hip) --------------------------------------
 int gm_kzg_srs_lagrange(gm_ctx* ctx, int curve, const void* srs_dev, size_t n, void* lagrange_dev) {
+  if (int rc = check_curve(curve, CURVES_01, "gm_kzg_srs_lagrange")) return rc;
   if (!ctx || !srs_dev || !lagrange_dev) return refuse_null("kzg srs lagrange");
-  if (int rc = check_curve(curve)) return rc;
   // in place or disjoint: the last pass writes while other lanes may still read
   const uintptr_t a = (uintptr_t)srs_dev, b = (uintptr_t)lagrange_dev;
   const size_t len = 2 * fp_bytes(curve) * n;
@@ -1089,14 +1071,13 @@ int gm_kzg_srs_lagrange(gm_ctx* ctx, int curve, const void* srs_dev, size_t n, v
   }
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  return curve == GM_BN254 ? kzg_srs_lagrange_device<CurveBN254>(ctx, srs_dev, n, lagrange_dev)
-                           : kzg_srs_lagrange_device<CurveBLS12377>(ctx, srs_dev, n, lagrange_dev);
+  return GM_CURVE01(curve, kzg_srs_lagrange_device<C>(ctx, srs_dev, n, lagrange_dev));
 }
 
 int gm_plonk_sigma(gm_ctx* ctx, int curve, size_t n, const int64_t* perm_host, void* s1_dev, void* s2_dev,
                    void* s3_dev) {
+  if (int rc = check_curve(curve, CURVES_01, "gm_plonk_sigma")) return rc;
   if (!ctx || !perm_host || !s1_dev || !s2_dev || !s3_dev) return refuse_null("plonk sigma");
-  if (int rc = check_curve(curve)) return rc;
   if (n == 0 || (n & (n - 1)) || n > (size_t(1) << 30)) {
     set_error("plonk sigma: n must be a power of two, 2 <= n <= 2^30");
     return GM_ERR_INVALID;
@@ -1104,14 +1085,13 @@ int gm_plonk_sigma(gm_ctx* ctx, int curve, size_t n, const int64_t* perm_host, v
   if (int rc = plonk_perm_check(n, perm_host)) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  return curve == GM_BN254 ? plonk_sigma_device<CurveBN254>(ctx, n, perm_host, s1_dev, s2_dev, s3_dev)
-                           : plonk_sigma_device<CurveBLS12377>(ctx, n, perm_host, s1_dev, s2_dev, s3_dev);
+  return GM_CURVE01(curve, plonk_sigma_device<C>(ctx, n, perm_host, s1_dev, s2_dev, s3_dev));
 }
 
 int gm_plonk_pk_setup(gm_ctx* ctx, int curve, const gm_plonk_setup_host* in, unsigned flags, gm_plonk_pk** out,
                       void* vk_digests, void* srs_lagrange_out) {
+  if (int rc = check_curve(curve, CURVES_01, "gm_plonk_pk_setup")) return rc;
   if (!ctx || !in || !out) return refuse_null("plonk pk setup");
-  if (int rc = check_curve(curve)) return rc;
   return plonk_pk_setup(ctx, curve, in, flags, out, vk_digests, srs_lagrange_out);
 }
 
@@ -1121,8 +1101,8 @@ int gm_plonk_wires_permutation(gm_ctx* ctx, const gm_plonk_wires* w, int64_t* pe
 }
 
 int gm_plonk_sigma_wires(gm_ctx* ctx, int curve, const gm_plonk_wires* w, void* s1_dev, void* s2_dev, void* s3_dev) {
+  if (int rc = check_curve(curve, CURVES_01, "gm_plonk_sigma_wires")) return rc;
   if (!ctx || !w || !s1_dev || !s2_dev || !s3_dev) return refuse_null("plonk sigma wires");
-  if (int rc = check_curve(curve)) return rc;
   if (w->ctx != ctx) {
     set_error("plonk sigma wires: the tables were uploaded on another context");
     return GM_ERR_INVALID;
@@ -1133,24 +1113,22 @@ int gm_plonk_sigma_wires(gm_ctx* ctx, int curve, const gm_plonk_wires* w, void* 
   }
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  return curve == GM_BN254 ? plonk_sigma_wires_device<CurveBN254>(ctx, w, s1_dev, s2_dev, s3_dev)
-                           : plonk_sigma_wires_device<CurveBLS12377>(ctx, w, s1_dev, s2_dev, s3_dev);
+  return GM_CURVE01(curve, plonk_sigma_wires_device<C>(ctx, w, s1_dev, s2_dev, s3_dev));
 }
 
 int gm_plonk_pk_setup_wires(gm_ctx* ctx, int curve, const gm_plonk_setup_host* in, const gm_plonk_wires* w,
                             unsigned flags, gm_plonk_pk** out, void* vk_digests, void* srs_lagrange_out) {
+  if (int rc = check_curve(curve, CURVES_01, "gm_plonk_pk_setup_wires")) return rc;
   if (!ctx || !in || !w || !out) return refuse_null("plonk pk setup wires");
-  if (int rc = check_curve(curve)) return rc;
   return plonk_pk_setup_wires(ctx, curve, in, w, flags, out, vk_digests, srs_lagrange_out);
 }
 
 // ---- NTT --------------------------------------------------------------------------
 int gm_ntt(gm_ctx* ctx, int curve, void* data_dev, size_t n, int inverse, int dit, int coset) {
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_ntt")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  int rc = curve == GM_BN254 ? ntt_device<CurveBN254>(ctx, data_dev, n, inverse, dit, coset)
-                             : ntt_device<CurveBLS12377>(ctx, data_dev, n, inverse, dit, coset);
+  int rc = GM_CURVE(curve, ntt_device<C>(ctx, data_dev, n, inverse, dit, coset));
   if (rc) return rc;
   GM_HIP(hipStreamSynchronize(ctx->stream));
   prof_collect(ctx);
@@ -1158,33 +1136,30 @@ int gm_ntt(gm_ctx* ctx, int curve, void* data_dev, size_t n, int inverse, int di
 }
 int gm_poly_ops(gm_ctx* ctx, int curve, void* a, const void* b, const void* c, size_t n,
                 const void* den_host) {
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_poly_ops")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  int rc = curve == GM_BN254 ? poly_ops_device<CurveBN254>(ctx, a, b, c, n, den_host)
-                             : poly_ops_device<CurveBLS12377>(ctx, a, b, c, n, den_host);
+  int rc = GM_CURVE(curve, poly_ops_device<C>(ctx, a, b, c, n, den_host));
   if (rc) return rc;
   GM_HIP(hipStreamSynchronize(ctx->stream));
   prof_collect(ctx);
   return GM_OK;
 }
 int gm_reverse_scalars(gm_ctx* ctx, int curve, void* data_dev, size_t n) {
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_reverse_scalars")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  int rc = curve == GM_BN254 ? reverse_device<CurveBN254>(ctx, data_dev, n)
-                             : reverse_device<CurveBLS12377>(ctx, data_dev, n);
+  int rc = GM_CURVE(curve, reverse_device<C>(ctx, data_dev, n));
   if (rc) return rc;
   GM_HIP(hipStreamSynchronize(ctx->stream));
   prof_collect(ctx);
   return GM_OK;
 }
 int gm_groth16_compute_h(gm_ctx* ctx, int curve, void* a, void* b, void* c, size_t len, size_t n) {
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_groth16_compute_h")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  int rc = curve == GM_BN254 ? compute_h_device<CurveBN254>(ctx, a, b, c, len, n)
-                             : compute_h_device<CurveBLS12377>(ctx, a, b, c, len, n);
+  int rc = GM_CURVE(curve, compute_h_device<C>(ctx, a, b, c, len, n));
   if (rc) return rc;
   GM_HIP(hipStreamSynchronize(ctx->stream));
   prof_collect(ctx);
@@ -1211,20 +1186,14 @@ static void jac_aff_t(const void* p, void* out) {
 }  // extern "C++"
 
 int gm_jac_add(int curve, int g2, const void* p, const void* q, void* out) {
-  if (int rc = check_curve(curve)) return rc;
-  if (curve == GM_BN254)
-    g2 ? jac_add_t<CurveBN254::HG2F>(p, q, out) : jac_add_t<CurveBN254::HG1F>(p, q, out);
-  else
-    g2 ? jac_add_t<CurveBLS12377::HG2F>(p, q, out) : jac_add_t<CurveBLS12377::HG1F>(p, q, out);
-  return GM_OK;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_jac_add")) return rc;
+  return GM_CURVE(curve, (g2 ? jac_add_t<typename C::HG2F>(p, q, out) : jac_add_t<typename C::HG1F>(p, q, out)),
+                  (int)GM_OK);
 }
 int gm_jac_to_affine(int curve, int g2, const void* p, void* out) {
-  if (int rc = check_curve(curve)) return rc;
-  if (curve == GM_BN254)
-    g2 ? jac_aff_t<CurveBN254::HG2F>(p, out) : jac_aff_t<CurveBN254::HG1F>(p, out);
-  else
-    g2 ? jac_aff_t<CurveBLS12377::HG2F>(p, out) : jac_aff_t<CurveBLS12377::HG1F>(p, out);
-  return GM_OK;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_jac_to_affine")) return rc;
+  return GM_CURVE(curve, (g2 ? jac_aff_t<typename C::HG2F>(p, out) : jac_aff_t<typename C::HG1F>(p, out)),
+                  (int)GM_OK);
 }
 
 // ---- synthetic inputs -------------------------------------------------------------------
@@ -1232,24 +1201,31 @@ static const uint64_t GEN_BN_G1[] = GM_BN254_G1_GEN64;
 static const uint64_t GEN_BN_G2[] = GM_BN254_G2_GEN64;
 static const uint64_t GEN_BLS_G1[] = GM_BLS12377_G1_GEN64;
 static const uint64_t GEN_BLS_G2[] = GM_BLS12377_G2_GEN64;
+static const uint64_t GEN_BLS381_G1[] = GM_BLS12381_G1_GEN64;
+static const uint64_t GEN_BLS381_G2[] = GM_BLS12381_G2_GEN64;
 
 int gm_generator(int curve, int g2, void* out) {
-  if (int rc = check_curve(curve)) return rc;
-  const uint64_t* src = curve == GM_BN254 ? (g2 ? GEN_BN_G2 : GEN_BN_G1) : (g2 ? GEN_BLS_G2 : GEN_BLS_G1);
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_generator")) return rc;
+  static const uint64_t* const gens[CURVE_COUNT][2] = {
+      {GEN_BN_G1, GEN_BN_G2}, {GEN_BLS_G1, GEN_BLS_G2}, {GEN_BLS381_G1, GEN_BLS381_G2}};
+  const uint64_t* src = gens[curve][g2 ? 1 : 0];
   memcpy(out, src, fp_bytes(curve) * (g2 ? 4 : 2));
   return GM_OK;
 }
 
 int gm_random_scalars(gm_ctx* ctx, int curve, uint64_t seed, size_t n, void* scalars_dev) {
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_random_scalars")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  if (curve == GM_BN254)
-    hipLaunchKernelGGL(k_random_scalars<Bn254Fr>, dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream,
-                       (uint32_t*)scalars_dev, n, seed);
-  else
-    hipLaunchKernelGGL(k_random_scalars<Bls377Fr>, dim3(blocks_for(n, 256)), dim3(256), 0,
-                       ctx->stream, (uint32_t*)scalars_dev, n, seed);
+  with_curve(
+      curve,
+      [&](auto tag_) {
+        using Fr = typename decltype(tag_)::type::Fr;
+        hipLaunchKernelGGL(k_random_scalars<Fr>, dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream,
+                           (uint32_t*)scalars_dev, n, seed);
+        return 0;
+      },
+      0);
   GM_HIP(hipGetLastError());
   GM_HIP(hipStreamSynchronize(ctx->stream));
   return GM_OK;
@@ -1271,14 +1247,11 @@ static int batch_mul_t(gm_ctx* ctx, const void* base, const void* sc, size_t n, 
 
 int gm_batch_mul_base(gm_ctx* ctx, int curve, int g2, const void* base, const void* sc, size_t n,
                       void* out) {
-  if (int rc = check_curve(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_01, "gm_batch_mul_base")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  if (curve == GM_BN254)
-    return g2 ? batch_mul_t<CurveBN254, true>(ctx, base, sc, n, out)
-              : batch_mul_t<CurveBN254, false>(ctx, base, sc, n, out);
-  return g2 ? batch_mul_t<CurveBLS12377, true>(ctx, base, sc, n, out)
-            : batch_mul_t<CurveBLS12377, false>(ctx, base, sc, n, out);
+  return GM_CURVE01(curve, g2 ? batch_mul_t<C, true>(ctx, base, sc, n, out)
+                               : batch_mul_t<C, false>(ctx, base, sc, n, out));
 }
 
 // ---- Groth16 setup: fixed-base batch multiplication (g16_setup.hip) --------------------
@@ -1295,19 +1268,16 @@ int gm_set_fixed_base_window(gm_ctx* ctx, int c) {
 }
 
 int gm_batch_mul_fixed(gm_ctx* ctx, int curve, int g2, const void* base, const void* sc, size_t n, void* out) {
+  if (int rc = check_curve(curve, CURVES_01, "gm_batch_mul_fixed")) return rc;
   if (!ctx || !base || (n && (!sc || !out))) return refuse_null("gm_batch_mul_fixed");
-  if (int rc = check_curve(curve)) return rc;
   if (n >= (size_t(1) << 32)) {
     set_error("gm_batch_mul_fixed: n must be below 2^32");
     return GM_ERR_INVALID;
   }
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  if (curve == GM_BN254)
-    return g2 ? batch_mul_fixed_device<CurveBN254, true>(ctx, base, sc, n, out)
-              : batch_mul_fixed_device<CurveBN254, false>(ctx, base, sc, n, out);
-  return g2 ? batch_mul_fixed_device<CurveBLS12377, true>(ctx, base, sc, n, out)
-            : batch_mul_fixed_device<CurveBLS12377, false>(ctx, base, sc, n, out);
+  return GM_CURVE01(curve, g2 ? batch_mul_fixed_device<C, true>(ctx, base, sc, n, out)
+                               : batch_mul_fixed_device<C, false>(ctx, base, sc, n, out));
 }
 
 // ---- Groth16 setup: the scalar side and the points (g16_setup.hip) ------------------------

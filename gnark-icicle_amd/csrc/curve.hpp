@@ -1,6 +1,6 @@
 // Device-side elliptic-curve arithmetic for the MSM bucket phase (gfx950).
 //
-// Curves: short Weierstrass y^2 = x^3 + b (a = 0) -- BN254 / BLS12-377, G1 over
+// Curves: short Weierstrass y^2 = x^3 + b (a = 0) -- BN254 / BLS12-377 / BLS12-381, G1 over
 // Fp and G2 over Fp2.  Points arrive in gnark-crypto's G1Affine / G2Affine memory
 // layout ({X, Y}, Montgomery limbs, infinity encoded as (0,0)).
 //
@@ -130,7 +130,8 @@ GM_DEV void xyzz_add_aff(XYZZ<F>& a, const Affine<F>& p) {
 // accumulation kernel only (GM_MSM_ACC_CHAIN=1).
 template <class P, int CH = 0>
 GM_DEV void xyzz_add_aff_lz(XYZZ<Fe<P>>& a, const Affine<Fe<P>>& p, bool neg) {
-  static_assert(P::BITS + 7 <= RADIX * P::N, "lazy reduction needs R' > 128 p");
+  GM_LAZY_BOUND(P, 100, "G1 mixed add: P^2 with P < 10p");
+  GM_LAZY_BOUND(P, 76, "G1 mixed add: R (Q - X3 + 9p) + (5p - Y1) PPP");
   using F = Fe<P>;
   if (aff_is_inf(p)) return;
   if (xyzz_is_inf(a)) {
@@ -178,7 +179,8 @@ GM_DEV void xyzz_add_aff_lz(XYZZ<Fe<P>>& a, const Affine<Fe<P>>& p, bool neg) {
 // below 4p per component (see fe2_mul_lz / fe2_sqr_lz).
 template <class P, int BETA>
 GM_DEV void xyzz_add_aff_lz(XYZZ<Fe2<P, BETA>>& a, const Affine<Fe2<P, BETA>>& p) {
-  static_assert(P::BITS + 7 <= RADIX * P::N, "lazy reduction needs R' > 128 p");
+  // components stay below 4p at every product: fe2_mul_lz / fe2_sqr_lz<4> assert their own bounds
+  GM_LAZY_BOUND(P, 64, "G2 one-lane mixed add: (a0 + a1)(b0 + b1) with components < 4p");
   using F = Fe2<P, BETA>;
   if (aff_is_inf(p)) return;
   if (xyzz_is_inf(a)) {
@@ -285,6 +287,7 @@ GM_DEV XYZZ<Fe<P>> xyzz_canon_raw(const XYZZ<Fe<P>>& a) {
 template <class P>
 GM_DEV XYZZ<Fe<P>> xyzz_add_lz(const XYZZ<Fe<P>>& a, const XYZZ<Fe<P>>& b) {
   using F = Fe<P>;
+  GM_LAZY_BOUND(P, 22, "G1 full add: 8p 2p = 16 p^2; Y3's two products 22 p^2");
   if (xyzz_is_inf(a)) return b;
   if (xyzz_is_inf(b)) return a;
   const F U1 = fe_mul_lz(a.x, b.zz);  // < 2p
@@ -367,5 +370,6 @@ GM_DEV XYZZ<F> xyzz_mul_small(const XYZZ<F>& a, uint32_t k) {
 // Curve bundles ---------------------------------------------------------------
 using Bn254Fp2 = Fe2<Bn254Fp, -1>;
 using Bls377Fp2 = Fe2<Bls377Fp, -5>;
+using Bls381Fp2 = Fe2<Bls381Fp, -1>;
 
 }  // namespace gm

@@ -9,7 +9,7 @@
 //
 //  * internal (registers / LDS / device scratch): N unsaturated 29-bit limbs
 //    (radix 2^29, one limb per u32) in Montgomery form x*R' mod p,
-//    R' = 2^(29N) (N = 9 for the 254/253-bit fields, 14 for BLS12-377 Fp).
+//    R' = 2^(29N) (N = 9 for the 253- to 255-bit fields, 14 for the BLS12 Fp).
 //    Values are kept canonical (< p, every limb < 2^29).
 //
 // Why radix 2^29: a finely-integrated product-scanning Montgomery product then
@@ -46,6 +46,8 @@ constexpr uint32_t LIMB_MASK = (1u << RADIX) - 1;
     static constexpr int NG = GM_##TAG##_NG;  /* gnark u32 words */             \
     static constexpr int BITS = GM_##TAG##_BITS;                                \
     static constexpr uint32_t INV = GM_##TAG##_INV29;                           \
+    /* floor(R' / p): a b < HEADROOM p^2 keeps a lazy product below 2p */       \
+    static constexpr uint64_t HEADROOM = GM_##TAG##_HEADROOM;                   \
     GM_CONST_ARRAY_FN(p, GM_##TAG##_N29, GM_##TAG##_P29)                        \
     GM_CONST_ARRAY_FN(one, GM_##TAG##_N29, GM_##TAG##_ONE29)                    \
     GM_CONST_ARRAY_FN(r2, GM_##TAG##_N29, GM_##TAG##_R229)                      \
@@ -69,6 +71,8 @@ GM_DEFINE_FIELD(Bn254Fp, BN254_FP)
 GM_DEFINE_FIELD(Bn254Fr, BN254_FR)
 GM_DEFINE_FIELD(Bls377Fp, BLS12377_FP)
 GM_DEFINE_FIELD(Bls377Fr, BLS12377_FR)
+GM_DEFINE_FIELD(Bls381Fp, BLS12381_FP)
+GM_DEFINE_FIELD(Bls381Fr, BLS12381_FR)
 
 template <class P>
 struct Fe {
@@ -378,9 +382,13 @@ GM_DEV Fe<P> fe_sqr(const Fe<P>& a) {
 // subtraction (a third of the product's non-multiply instructions) can go.
 // fe_sub_lz<K> adds K p instead of testing the sign.  The accumulation keeps
 // x < 8p, y < 4p, zz, zzz < 2p and every product input pair satisfies
-// ab <= 100 p^2 < R' p, which needs R' / p > 100 (static_assert in the caller:
-// BITS + 7 <= 29 N, i.e. R' / p > 128; BN254 Fp: 254 + 7 = 261 = 29 * 9).
+// ab <= 100 p^2 < R' p, which needs R' / p > 100.  Every function below and in
+// curve.hpp / pair_fp2.hpp that relies on such a bound asserts it against the
+// field's generated headroom P::HEADROOM = floor(R' / p) (GM_LAZY_BOUND): a
+// product of operands below a p and b p needs a b <= HEADROOM (BN254 Fp: 169).
 // ---------------------------------------------------------------------------
+#define GM_LAZY_BOUND(P, K, what) \
+  static_assert((uint64_t)(K) <= P::HEADROOM, what ": product bound exceeds R' / p (HEADROOM)")
 // limb i of K*p, normalised radix 2^29 (the top limb keeps any excess)
 template <class P, int K>
 GM_HD constexpr uint32_t kp_limb(int i) {
@@ -739,6 +747,7 @@ GM_DEV Fe<P> fe_times5_lz(const Fe<P>& x) {
 // Karatsuba product, result components < 2p.  Inputs: components < 6p (BN254).
 template <class P, int BETA>
 GM_DEV Fe2<P, BETA> fe2_mul_lz(const Fe2<P, BETA>& a, const Fe2<P, BETA>& b) {
+  GM_LAZY_BOUND(P, 144, "fe2_mul_lz: (a0 + a1)(b0 + b1) with components < 6p");
   const Fe<P> v0 = fe_mul_lz(a.a0, b.a0);  // < 2p
   const Fe<P> v1 = fe_mul_lz(a.a1, b.a1);  // < 2p
   const Fe<P> s = fe_mul_lz(fe_add_lz(a.a0, a.a1), fe_add_lz(b.a0, b.a1));  // < 2p
@@ -758,6 +767,8 @@ GM_DEV Fe2<P, BETA> fe2_mul_lz(const Fe2<P, BETA>& a, const Fe2<P, BETA>& b) {
 // Complex squaring, result components < 2p.  Inputs: components < IN p.
 template <int IN, class P, int BETA>
 GM_DEV Fe2<P, BETA> fe2_sqr_lz(const Fe2<P, BETA>& a) {
+  // BETA = -1: (2 IN p)^2; BETA = -5: (2 IN p)(a0 - 5 a1 + 5 IN p < 6 IN p)
+  GM_LAZY_BOUND(P, (BETA == -1 ? 4 : 12) * IN * IN, "fe2_sqr_lz");
   const Fe<P> c = fe_mul_lz(a.a0, a.a1);  // < 2p
   Fe2<P, BETA> r;
   if constexpr (BETA == -1) {

@@ -44,13 +44,8 @@ static bool cross_device(int a, int b) {
   return f && atoi(f) != 0;
 }
 
-int check_curve_id(int curve) {
-  if (curve != GM_BN254 && curve != GM_BLS12_377) {
-    set_error("unknown curve id");
-    return GM_ERR_INVALID;
-  }
-  return GM_OK;
-}
+// capability check of the deferred entries (curves 0 and 1; BLS12-381 is refused)
+int check_curve_id(int curve, const char* entry) { return check_curve(curve, CURVES_01, entry); }
 
 namespace {
 // dst[i] = src[idx[i]] (Fr, 32 bytes) -- device-side scalar compaction
@@ -84,9 +79,13 @@ void shard_weighted(size_t n, const std::vector<double>& w, int k, size_t* lo, s
 }  // namespace
 
 size_t internal_point_bytes(int curve, bool g2) {
-  if (curve == GM_BN254)
-    return g2 ? msm_internal_point_bytes<CurveBN254, true>() : msm_internal_point_bytes<CurveBN254, false>();
-  return g2 ? msm_internal_point_bytes<CurveBLS12377, true>() : msm_internal_point_bytes<CurveBLS12377, false>();
+  return with_curve(
+      curve,
+      [&](auto tag_) {
+        using C = typename decltype(tag_)::type;
+        return g2 ? msm_internal_point_bytes<C, true>() : msm_internal_point_bytes<C, false>();
+      },
+      (size_t)0);
 }
 
 void pk_release(gm_g16_pk* pk) {
@@ -144,17 +143,11 @@ __global__ void k_expand_points(const uint4* __restrict__ src, size_t cnt, const
 int prepare_points_into(gm_ctx* ctx, int curve, bool g2, const void* gnark_dev, size_t count,
                         const MsmPrecomp* pre, void* dst) {
   if (pre) {
-    if (curve == GM_BN254)
-      return g2 ? msm_precompute_points<CurveBN254, true>(ctx, gnark_dev, count, *pre, dst)
-                : msm_precompute_points<CurveBN254, false>(ctx, gnark_dev, count, *pre, dst);
-    return g2 ? msm_precompute_points<CurveBLS12377, true>(ctx, gnark_dev, count, *pre, dst)
-              : msm_precompute_points<CurveBLS12377, false>(ctx, gnark_dev, count, *pre, dst);
+    return GM_CURVE(curve, g2 ? msm_precompute_points<C, true>(ctx, gnark_dev, count, *pre, dst)
+                              : msm_precompute_points<C, false>(ctx, gnark_dev, count, *pre, dst));
   }
-  if (curve == GM_BN254)
-    return g2 ? msm_prepare_points<CurveBN254, true>(ctx, gnark_dev, count, dst)
-              : msm_prepare_points<CurveBN254, false>(ctx, gnark_dev, count, dst);
-  return g2 ? msm_prepare_points<CurveBLS12377, true>(ctx, gnark_dev, count, dst)
-            : msm_prepare_points<CurveBLS12377, false>(ctx, gnark_dev, count, dst);
+  return GM_CURVE(curve, g2 ? msm_prepare_points<C, true>(ctx, gnark_dev, count, dst)
+                            : msm_prepare_points<C, false>(ctx, gnark_dev, count, dst));
 }
 
 // Uploads the [lo, hi) slices of the key's point arrays (h's pointers address
@@ -175,7 +168,7 @@ int pk_upload_ranges(gm_ctx* ctx, int curve, const gm_g16_pk_host* h, unsigned f
   pk->nbZ = rg.hiZ - rg.loZ;
   pk->precomp = (flags & GM_PK_PRECOMPUTE) != 0;
   const bool precomp_auto = !pk->precomp && (flags & GM_PK_PRECOMPUTE_AUTO);
-  const int frbits = curve == GM_BN254 ? CurveBN254::FR_BITS : CurveBLS12377::FR_BITS;
+  const int frbits = fr_bits(curve);
   auto fail = [&](int code) {
     pk_release(pk);
     return code;
@@ -409,8 +402,7 @@ int pk_upload_ranges(gm_ctx* ctx, int curve, const gm_g16_pk_host* h, unsigned f
 
 void pk_prepare_h(gm_ctx* ctx, const gm_g16_pk* pk) {
   const std::string saved = last_error();
-  const int rc = pk->curve == GM_BN254 ? compute_h_prepare<CurveBN254>(ctx, pk->n)
-                                       : compute_h_prepare<CurveBLS12377>(ctx, pk->n);
+  const int rc = GM_CURVE(pk->curve, compute_h_prepare<C>(ctx, pk->n));
   if (rc) {  // e.g. out of memory: the first prove builds them (or reports it); the upload succeeded
     (void)hipGetLastError();
     set_error(saved);
@@ -1184,13 +1176,11 @@ int gm_g16_pk_upload(gm_ctx* ctx, int curve, const gm_g16_pk_host* h, gm_g16_pk*
   return gm_g16_pk_upload_ex(ctx, curve, h, 0u, out);
 }
 
-int gm_g16_pk_upload_ex(gm_ctx* ctx, int curve, const gm_g16_pk_host* h, unsigned flags, gm_g16_pk** out) {
-  return gm_g16_pk_upload_shard(ctx, curve, h, flags, 0, 1, out);
-}
+}  // extern "C"
 
-int gm_g16_pk_upload_shard(gm_ctx* ctx, int curve, const gm_g16_pk_host* h, unsigned flags, int rank, int world,
+// the whole key (rank 0 of 1) or one rank's share of it; the curve is checked by the entries
+static int pk_upload_share(gm_ctx* ctx, int curve, const gm_g16_pk_host* h, unsigned flags, int rank, int world,
                            gm_g16_pk** out) {
-  if (int rc = check_curve_id(curve)) return rc;
   if (flags & ~(unsigned)(GM_PK_PRECOMPUTE | GM_PK_PRECOMPUTE_AUTO)) {
     set_error("pk upload: unknown flags");
     return GM_ERR_INVALID;
@@ -1209,6 +1199,19 @@ int gm_g16_pk_upload_shard(gm_ctx* ctx, int curve, const gm_g16_pk_host* h, unsi
   shard_of(h->domain_size - 1, rank, world, &rg.loZ, &rg.hiZ);
   rg.rebase = false;
   return pk_upload_ranges(ctx, curve, h, flags, rg, out, nullptr);
+}
+
+extern "C" {
+
+int gm_g16_pk_upload_ex(gm_ctx* ctx, int curve, const gm_g16_pk_host* h, unsigned flags, gm_g16_pk** out) {
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_g16_pk_upload")) return rc;
+  return pk_upload_share(ctx, curve, h, flags, 0, 1, out);
+}
+
+int gm_g16_pk_upload_shard(gm_ctx* ctx, int curve, const gm_g16_pk_host* h, unsigned flags, int rank, int world,
+                           gm_g16_pk** out) {
+  if (int rc = check_curve_id(curve, "gm_g16_pk_upload_shard")) return rc;
+  return pk_upload_share(ctx, curve, h, flags, rank, world, out);
 }
 
 int gm_g16_pk_precomputed(const gm_g16_pk* pk, int* out) {
@@ -1234,10 +1237,7 @@ int gm_g16_prove_device(gm_ctx* ctx, gm_g16_pk* pk, const void* wires_dev, void*
   }
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  int rc = pk->curve == GM_BN254 ? g16_prove_t<CurveBN254>(ctx, pk, wires_dev, a, b, c, nullptr, nullptr, nullptr,
-                                                           nc, r, s, ar_out, bs_out, krs_out)
-                                 : g16_prove_t<CurveBLS12377>(ctx, pk, wires_dev, a, b, c, nullptr, nullptr, nullptr,
-                                                              nc, r, s, ar_out, bs_out, krs_out);
+  int rc = GM_CURVE(pk->curve, g16_prove_t<C>(ctx, pk, wires_dev, a, b, c, nullptr, nullptr, nullptr, nc, r, s, ar_out, bs_out, krs_out));
   prof_collect(ctx);
   return rc;
 }
@@ -1264,10 +1264,7 @@ int gm_g16_prove(gm_ctx* ctx, gm_g16_pk* pk, const void* wires, const void* a, c
   char* const db = da + 32 * pk->n;
   char* const dc = db + 32 * pk->n;
   GM_HIP(hipMemcpyAsync(w.p, wires, 32 * pk->nb_wires, hipMemcpyHostToDevice, ctx->stream));
-  rc = pk->curve == GM_BN254 ? g16_prove_t<CurveBN254>(ctx, pk, w.p, da, db, dc, a, b, c, nc, r, s, ar_out,
-                                                       bs_out, krs_out)
-                             : g16_prove_t<CurveBLS12377>(ctx, pk, w.p, da, db, dc, a, b, c, nc, r, s, ar_out,
-                                                          bs_out, krs_out);
+  rc = GM_CURVE(pk->curve, g16_prove_t<C>(ctx, pk, w.p, da, db, dc, a, b, c, nc, r, s, ar_out, bs_out, krs_out));
   prof_collect(ctx);
   return rc;
 }
@@ -1286,11 +1283,7 @@ int gm::g16_prove_r1cs_device(gm_ctx* ctx, gm_g16_pk* pk, const gm_r1cs* r1, con
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
   const size_t nc = r1cs_nb_constraints(r1);
-  int rc = pk->curve == GM_BN254
-               ? g16_prove_t<CurveBN254>(ctx, pk, wires_dev, a, b, c, nullptr, nullptr, nullptr, nc, r, s, ar_out,
-                                         bs_out, krs_out, r1)
-               : g16_prove_t<CurveBLS12377>(ctx, pk, wires_dev, a, b, c, nullptr, nullptr, nullptr, nc, r, s,
-                                            ar_out, bs_out, krs_out, r1);
+  int rc = GM_CURVE(pk->curve, g16_prove_t<C>(ctx, pk, wires_dev, a, b, c, nullptr, nullptr, nullptr, nc, r, s, ar_out, bs_out, krs_out, r1));
   prof_collect(ctx);
   return rc;
 }
@@ -1305,6 +1298,7 @@ extern "C" {
 int gm_g16_prove_r1cs(gm_ctx* ctx, gm_g16_pk* pk, const gm_r1cs* r1, const void* wires, const void* r,
                       const void* s, void* ar_out, void* bs_out, void* krs_out) {
   if (!ctx || !pk || !r1 || !wires || !r || !s || !ar_out || !bs_out || !krs_out) return GM_ERR_INVALID;
+  if (int rc = check_curve_id(pk->curve, "gm_g16_prove_r1cs")) return rc;
   if (!r1cs_matches_key(pk, r1)) {
     set_error("prove_r1cs: constraint system does not match the proving key (constraints <= n, same wires, "
               "whole key)");
@@ -1324,7 +1318,7 @@ int gm_g16_prove_r1cs(gm_ctx* ctx, gm_g16_pk* pk, const gm_r1cs* r1, const void*
 
 // ---- sharded Groth16 (one process per GPU) --------------------
 int gm_g16_partial_bytes(int curve, size_t* out) {
-  if (int rc = check_curve_id(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_g16_partial_bytes")) return rc;
   if (out) *out = 4 * 3 * fp_bytes(curve) + 3 * 2 * fp_bytes(curve);
   return GM_OK;
 }
@@ -1332,6 +1326,7 @@ int gm_g16_partial_bytes(int curve, size_t* out) {
 int gm_g16_prove_partial(gm_ctx* ctx, gm_g16_pk* pk, const void* wires_dev, void* a_dev, void* b_dev, void* c_dev,
                          size_t nc, void* partial_out) {
   if (!ctx || !pk || !partial_out) return GM_ERR_INVALID;
+  if (int rc = check_curve_id(pk->curve, "gm_g16_prove_partial")) return rc;
   if (nc > pk->n) {
     set_error("prove: more constraints than the domain size");
     return GM_ERR_INVALID;
@@ -1339,7 +1334,7 @@ int gm_g16_prove_partial(gm_ctx* ctx, gm_g16_pk* pk, const void* wires_dev, void
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
   auto run = [&](auto tag) -> int {
-    using C = decltype(tag);
+    using C = typename decltype(tag)::type;
     DeviceH<C> hs(ctx, pk, a_dev, b_dev, c_dev, nc);
     int rc;
     if ((rc = hs.start())) return rc;
@@ -1348,27 +1343,26 @@ int gm_g16_prove_partial(gm_ctx* ctx, gm_g16_pk* pk, const void* wires_dev, void
     sums_to_bytes<C>(sums, (uint8_t*)partial_out);
     return GM_OK;
   };
-  int rc = pk->curve == GM_BN254 ? run(CurveBN254()) : run(CurveBLS12377());
+  int rc = with_curve01(pk->curve, run, (int)GM_ERR_INVALID);
   prof_collect(ctx);
   return rc;
 }
 
 int gm_g16_finish(int curve, const gm_g16_pk_host* h, const void* sums, const void* r, const void* s, void* ar_out,
                   void* bs_out, void* krs_out) {
-  if (int rc = check_curve_id(curve)) return rc;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_g16_finish")) return rc;
   if (!h || !sums || !r || !s || !ar_out || !bs_out || !krs_out) return GM_ERR_INVALID;
-  auto run = [&](auto tag) {
-    using C = decltype(tag);
+  auto run = [&](auto tag) -> int {
+    using C = typename decltype(tag)::type;
     G16Finish<C> fin((const uint8_t*)h->g1_alpha, (const uint8_t*)h->g1_beta, (const uint8_t*)h->g1_delta,
                      (const uint8_t*)h->g2_beta, (const uint8_t*)h->g2_delta, r, s);
     fin.begin();
     G16Sums<C> sm;
     bytes_to_sums<C>((const uint8_t*)sums, sm);
     fin.finish(sm, ar_out, bs_out, krs_out);
+    return GM_OK;
   };
-  if (curve == GM_BN254) run(CurveBN254());
-  else run(CurveBLS12377());
-  return GM_OK;
+  return with_curve(curve, run, (int)GM_ERR_INVALID);
 }
 
 }  // extern "C"
@@ -1437,8 +1431,8 @@ int gm_multi_context(gm_multi* m, int index, gm_ctx** out) {
 }
 
 int gm_g16_pk_upload_multi(gm_multi* m, int curve, const gm_g16_pk_host* h, unsigned flags, gm_g16_pk_multi** out) {
+  if (int rc = check_curve_id(curve, "gm_g16_pk_upload_multi")) return rc;
   if (!m || !h || !out || h->domain_size < 2) return GM_ERR_INVALID;
-  if (int rc = check_curve_id(curve)) return rc;
   const int nd = (int)m->ctx.size();
   // device 0 also runs computeH (~19 ms at 2^24): it takes a smaller share of
   // the MSM work (GM_MULTI_SHARE0 = its weight relative to the others' 1.0)
@@ -1697,10 +1691,8 @@ int gm_g16_prove_multi(gm_multi* m, gm_g16_pk_multi* mp, const void* wires, cons
     set_error("prove: more constraints than the domain size");
     return GM_ERR_INVALID;
   }
-  int rc = mp->curve == GM_BN254
-               ? g16_prove_multi_t<CurveBN254>(m, mp, (const uint8_t*)wires, a, b, c, nc, r, s, ar_out, bs_out, krs_out)
-               : g16_prove_multi_t<CurveBLS12377>(m, mp, (const uint8_t*)wires, a, b, c, nc, r, s, ar_out, bs_out,
-                                                  krs_out);
+  int rc = GM_CURVE01(mp->curve, g16_prove_multi_t<C>(m, mp, (const uint8_t*)wires, a, b, c, nc, r, s, ar_out,
+                                                       bs_out, krs_out));
   for (gm_ctx* x : m->ctx) prof_collect(x);
   return rc;
 }

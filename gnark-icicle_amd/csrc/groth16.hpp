@@ -59,7 +59,7 @@ struct Ranges {
 // pre->W copies when pre != nullptr) with `count` points of key array `which`.
 using PointSource = std::function<int(int which, size_t count, bool g2, const MsmPrecomp* pre, void* dst)>;
 
-int check_curve_id(int curve);
+int check_curve_id(int curve, const char* entry);  // curves 0 and 1; BLS12-381: GM_ERR_UNSUPPORTED
 size_t internal_point_bytes(int curve, bool g2);
 void pk_release(gm_g16_pk* pk);
 void stage_spare_release(gm_g16_pk* pk);  // pk_io.hip

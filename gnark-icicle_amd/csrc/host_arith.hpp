@@ -27,6 +27,8 @@ GM_HOST_FIELD(HBnFp, BN254_FP, 4)
 GM_HOST_FIELD(HBnFr, BN254_FR, 4)
 GM_HOST_FIELD(HBlsFp, BLS12377_FP, 6)
 GM_HOST_FIELD(HBlsFr, BLS12377_FR, 4)
+GM_HOST_FIELD(HBls381Fp, BLS12381_FP, 6)
+GM_HOST_FIELD(HBls381Fr, BLS12381_FR, 4)
 
 template <class D>
 struct F {

@@ -21,13 +21,8 @@ using namespace gm;
 
 namespace {
 
-int check_curve_id(int curve) {
-  if (curve != GM_BN254 && curve != GM_BLS12_377) {
-    set_error("unknown curve id");
-    return GM_ERR_INVALID;
-  }
-  return GM_OK;
-}
+// the gm_icicle_* calls serve curves 0 and 1; BLS12-381 is refused (GM_ERR_UNSUPPORTED)
+int check_curve_id(int curve, const char* entry) { return check_curve(curve, CURVES_01, entry); }
 
 template <class C>
 int intt_fresh(gm_ctx* ctx, void* in, size_t n, bool coset, void* out) {
@@ -56,11 +51,11 @@ extern "C" {
 
 int gm_icicle_generate_twiddles(gm_ctx* ctx, int curve, size_t n, int inverse, void** token_out) {
   (void)inverse;  // one cached domain serves both directions
+  if (int rc = check_curve_id(curve, "gm_icicle_generate_twiddles")) return rc;
   if (!ctx || !token_out) return GM_ERR_INVALID;
-  if (int rc = check_curve_id(curve)) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  int rc = curve == GM_BN254 ? ntt_domain_prepare<CurveBN254>(ctx, n) : ntt_domain_prepare<CurveBLS12377>(ctx, n);
+  int rc = GM_CURVE01(curve, ntt_domain_prepare<C>(ctx, n));
   if (rc) return rc;
   GM_HIP(hipStreamSynchronize(ctx->stream));
   // a real (freeable) allocation standing for the twiddle table handle
@@ -73,8 +68,8 @@ int gm_icicle_generate_twiddles(gm_ctx* ctx, int curve, size_t n, int inverse, v
 }
 
 int gm_icicle_intt_on_device(gm_ctx* ctx, int curve, void* in_dev, size_t n, int coset, void** out_dev) {
+  if (int rc = check_curve_id(curve, "gm_icicle_intt_on_device")) return rc;
   if (!ctx || !in_dev || !out_dev) return GM_ERR_INVALID;
-  if (int rc = check_curve_id(curve)) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
   void* out = nullptr;
@@ -83,8 +78,7 @@ int gm_icicle_intt_on_device(gm_ctx* ctx, int curve, void* in_dev, size_t n, int
     set_error(std::string("hipMalloc: ") + hipGetErrorString(e));
     return GM_ERR_OOM;
   }
-  int rc = curve == GM_BN254 ? intt_fresh<CurveBN254>(ctx, in_dev, n, coset != 0, out)
-                             : intt_fresh<CurveBLS12377>(ctx, in_dev, n, coset != 0, out);
+  int rc = GM_CURVE01(curve, intt_fresh<C>(ctx, in_dev, n, coset != 0, out));
   if (rc == GM_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) {
     set_error("gm_icicle_intt_on_device: stream synchronisation failed");
     rc = GM_ERR_DEVICE;
@@ -99,12 +93,11 @@ int gm_icicle_intt_on_device(gm_ctx* ctx, int curve, void* in_dev, size_t n, int
 }
 
 int gm_icicle_ntt_on_device(gm_ctx* ctx, int curve, void* out_dev, const void* in_dev, size_t n, int coset) {
+  if (int rc = check_curve_id(curve, "gm_icicle_ntt_on_device")) return rc;
   if (!ctx || !in_dev || !out_dev) return GM_ERR_INVALID;
-  if (int rc = check_curve_id(curve)) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  int rc = curve == GM_BN254 ? ntt_into<CurveBN254>(ctx, out_dev, in_dev, n, coset != 0)
-                             : ntt_into<CurveBLS12377>(ctx, out_dev, in_dev, n, coset != 0);
+  int rc = GM_CURVE01(curve, ntt_into<C>(ctx, out_dev, in_dev, n, coset != 0));
   if (rc) return rc;
   GM_HIP(hipStreamSynchronize(ctx->stream));
   prof_collect(ctx);
@@ -113,12 +106,11 @@ int gm_icicle_ntt_on_device(gm_ctx* ctx, int curve, void* out_dev, const void* i
 
 int gm_icicle_poly_ops(gm_ctx* ctx, int curve, void* a_dev, const void* b_dev, const void* c_dev,
                        const void* den_dev, size_t n) {
+  if (int rc = check_curve_id(curve, "gm_icicle_poly_ops")) return rc;
   if (!ctx || !a_dev || !b_dev || !c_dev || !den_dev) return GM_ERR_INVALID;
-  if (int rc = check_curve_id(curve)) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  int rc = curve == GM_BN254 ? poly_ops_vec_device<CurveBN254>(ctx, a_dev, b_dev, c_dev, den_dev, n)
-                             : poly_ops_vec_device<CurveBLS12377>(ctx, a_dev, b_dev, c_dev, den_dev, n);
+  int rc = GM_CURVE01(curve, poly_ops_vec_device<C>(ctx, a_dev, b_dev, c_dev, den_dev, n));
   if (rc) return rc;
   GM_HIP(hipStreamSynchronize(ctx->stream));
   prof_collect(ctx);

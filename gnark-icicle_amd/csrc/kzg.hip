@@ -405,5 +405,6 @@ int poly_fold_device(gm_ctx* ctx, const void* const* polys, const size_t* lens, 
   template int poly_fold_device<C>(gm_ctx*, const void* const*, const size_t*, size_t, const void*, void*);
 GM_KZG_INST(CurveBN254)
 GM_KZG_INST(CurveBLS12377)
+GM_KZG_INST(CurveBLS12381)
 
 }  // namespace gm

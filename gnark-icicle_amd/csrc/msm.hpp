@@ -97,6 +97,10 @@ inline int choose_window(size_t n, int bits) {
   return best;
 }
 
+// Bits the digits of one half of a GLV split cover: every curve's split leaves
+// |k1|, |k2| < 2^GLV_HALF_BITS (msm_impl.hpp, Glv<C>; GlvBls381 asserts it).
+constexpr int GLV_HALF_BITS = 127;
+
 // What msm_plan derives from (scalars, scalar bits, layout, window override)
 // before it allocates or launches anything.
 struct MsmPlanGeom {
@@ -117,7 +121,7 @@ inline const char* msm_plan_geom(size_t n0, int fr_bits, bool glv, const MsmPrec
   g.bits = fr_bits;
   if (glv) {  // virtual points: P_i and phi(P_i)
     n = 2 * n0;
-    g.bits = 127;
+    g.bits = GLV_HALF_BITS;
   }
   g.n = n;
   if (n >= (size_t(1) << 31)) return "msm: n must be < 2^31";
@@ -270,7 +274,7 @@ constexpr uint32_t PIECE_MAX_LEN = 128;  // length classes of the counting sort
 uint32_t msm_piece_len(const gm_ctx* ctx, size_t M);
 // Builds the piece plan of `plan` (offsets must be queued on ctx->stream).
 int msm_piece_plan(gm_ctx* ctx, Arena& arena, MsmPlan& plan, uint32_t T);
-// glv (plain layout, BN254 and BLS12-377): each scalar k is split
+// glv (plain layout, all three curves): each scalar k is split
 // k = k1 + k2 lambda with |k1|, |k2| < 2^127, over 2n points
 // [P_0..P_{n-1}, phi(P_0)..phi(P_{n-1})] (msm_device_launch builds them): half
 // the windows, so half the buckets to reduce, for the same number of bucket adds.

@@ -217,6 +217,56 @@ struct GlvBls377 {
   }
 };
 
+// ---------------------------------------------------------------------------
+// GLV split for BLS12-381: lambda = x^2 - 1 (x = -0xd201000000010000, the curve
+// seed) is a cube root of unity mod r = lambda^2 + lambda + 1, but lambda ~
+// 2^127.43: the halves of BLS12-377's unsigned division split (up to lambda) do
+// not fit the GLV_HALF_BITS = 127 bits the digit geometry covers.  The split is
+// signed and balanced instead: k > (r - 1) / 2 becomes r - k with both halves
+// negated; then k2 = round(k / lambda), k1 = k - k2 lambda, so |k1| <=
+// (lambda - 1) / 2 and 0 <= k2 <= (lambda + 1) / 2 + 1, both below 2^126.44, and
+// the window count at c = 16 stays 8.  q = floor(k g / 2^384), g = floor(2^384 /
+// lambda), is floor(k / lambda), or one less when lambda divides k, so
+// r0 = k - q lambda lies in [0, lambda]: exact mod 2^128.
+// phi(x, y) = (beta x, y) on G1, (beta^2 x, y) on the G2 twist.  Constants and
+// the split's model (200,000 scalars and the special ones): tools/glv_constants.py.
+// ---------------------------------------------------------------------------
+struct GlvBls381 {
+  GM_HD static constexpr uint64_t g(int i) {
+    constexpr uint64_t a[5] = {0xda5e4f8d896c72ddull, 0x389f49a7268bf7a3ull, 0x63f6e522f6cfee30ull,
+                               0x7c6becf1e01faaddull, 0x0000000000000001ull};
+    return a[i];
+  }
+  static constexpr uint64_t LAM_LO = 0x00000000ffffffffull, LAM_HI = 0xac45a4010001a402ull;
+  GM_HD static constexpr uint64_t r(int i) {
+    constexpr uint64_t a[4] = GM_BLS12381_FR_P64;
+    return a[i];
+  }
+  // (r - 1) / 2: scalars above it are split as r - k
+  GM_HD static constexpr uint64_t half(int i) {
+    constexpr uint64_t a[4] = {0x7fffffff80000000ull, 0xa9ded2017fff2dffull, 0x199cec0404d0ec02ull,
+                               0x39f6d3a994cebea4ull};
+    return a[i];
+  }
+  // largest half: k2 <= (lambda + 1) / 2 + 1 (|k1| <= (lambda - 1) / 2 is smaller)
+  static constexpr unsigned __int128 MAX_HALF =
+      ((((unsigned __int128)LAM_HI << 64) | LAM_LO) + 1) / 2 + 1;
+  static_assert(MAX_HALF < ((unsigned __int128)1 << GLV_HALF_BITS),
+                "the halves of the balanced split must fit the digits of a GLV plan");
+  GM_HD static constexpr uint32_t beta29(int i) {
+    constexpr uint32_t a[14] = {0x1195dfebu, 0x1b04e484u, 0x06026044u, 0x086070a2u, 0x1fd68858u,
+                                0x137e9670u, 0x06871e67u, 0x1e736664u, 0x083b24f6u, 0x08a70373u,
+                                0x02a012fdu, 0x0112f94bu, 0x18a2733cu, 0x00000003u};
+    return a[i];
+  }
+  GM_HD static constexpr uint32_t beta29_g2(int i) {
+    constexpr uint32_t a[14] = {0x0abf79e7u, 0x194b14ebu, 0x1ceb16a6u, 0x1845cd5du, 0x0c814568u,
+                                0x199ca109u, 0x13ee6ee1u, 0x05d123e5u, 0x0dfbdce2u, 0x010ecb54u,
+                                0x0d9337edu, 0x1daaf4b0u, 0x146806fbu, 0x0000000cu};
+    return a[i];
+  }
+};
+
 // beta of phi per base field: g1 for G1 points, g2 (= beta^2) for the G2 twist
 template <class P>
 struct GlvBeta;
@@ -229,6 +279,11 @@ template <>
 struct GlvBeta<Bls377Fp> {
   GM_HD static constexpr uint32_t g1(int i) { return GlvBls377::beta29(i); }
   GM_HD static constexpr uint32_t g2(int i) { return GlvBls377::beta29_g2(i); }
+};
+template <>
+struct GlvBeta<Bls381Fp> {
+  GM_HD static constexpr uint32_t g1(int i) { return GlvBls381::beta29(i); }
+  GM_HD static constexpr uint32_t g2(int i) { return GlvBls381::beta29_g2(i); }
 };
 
 // x -> beta x of the GLV endomorphism, G1 (Fp) and G2 (Fp2, beta in Fp)
@@ -289,14 +344,17 @@ GM_DEV void emit_digits(const FeG<Fr>& k, uint32_t flip, uint32_t i, const Digit
 }
 
 // Scalar split k = k1 + k2 lambda per curve: k1 in [0, 2^127), |k2| < 2^127,
-// neg2 = sign of k2 (BLS12-377: always 0).
+// neg2 = sign of k2 (BLS12-377: always 0).  signed_k1 (BLS12-381): k1 carries a
+// sign too, |k1| < 2^127, and split takes neg1.  2^127 is 2^GLV_HALF_BITS (msm.hpp).
 template <class C>
 struct Glv {
   static constexpr bool ok = false;
+  static constexpr bool signed_k1 = false;
 };
 template <>
 struct Glv<CurveBN254> {
   static constexpr bool ok = true;
+  static constexpr bool signed_k1 = false;
   using U = unsigned __int128;
   GM_DEV static void split(const uint64_t (&k64)[4], U& k1, U& k2, uint32_t& neg2) {
     const U c1 = glv_mulshift<5>(k64, GlvBn254::g1);
@@ -313,6 +371,7 @@ struct Glv<CurveBN254> {
 template <>
 struct Glv<CurveBLS12377> {
   static constexpr bool ok = true;
+  static constexpr bool signed_k1 = false;
   using U = unsigned __int128;
   GM_DEV static void split(const uint64_t (&k64)[4], U& k1, U& k2, uint32_t& neg2) {
     U q = glv_mulshift<5>(k64, GlvBls377::g);  // floor(k / lambda) or one less
@@ -326,6 +385,42 @@ struct Glv<CurveBLS12377> {
     k1 = r;
     k2 = q;
     neg2 = 0;
+  }
+};
+
+template <>
+struct Glv<CurveBLS12381> {
+  static constexpr bool ok = true;
+  static constexpr bool signed_k1 = true;
+  using U = unsigned __int128;
+  GM_DEV static void split(const uint64_t (&k64)[4], U& k1, uint32_t& neg1, U& k2, uint32_t& neg2) {
+    // flip = k > (r - 1) / 2: the borrow of (r - 1) / 2 - k; then kk = r - k
+    uint64_t kk[4], borrow = 0, b2 = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const U d = (U)GlvBls381::half(i) - k64[i] - borrow;
+      borrow = (uint64_t)(d >> 127) & 1;
+      const U e = (U)GlvBls381::r(i) - k64[i] - b2;
+      b2 = (uint64_t)(e >> 127) & 1;
+      kk[i] = (uint64_t)e;
+    }
+    const uint32_t flip = (uint32_t)borrow;
+#pragma unroll
+    for (int i = 0; i < 4; i++) kk[i] = flip ? kk[i] : k64[i];
+    U q = glv_mulshift<5>(kk, GlvBls381::g);  // floor(kk / lambda), or one less when lambda | kk
+    const U lam = ((U)GlvBls381::LAM_HI << 64) | GlvBls381::LAM_LO;
+    const U klo = ((U)kk[1] << 64) | kk[0];
+    U r0 = klo - q * lam;  // true value in [0, lambda]: exact mod 2^128
+    neg1 = 0;
+    if (r0 > (lam >> 1)) {  // round to nearest: k1 = r0 - lambda
+      r0 = lam - r0;
+      q += 1;
+      neg1 = 1;
+    }
+    k1 = r0;
+    k2 = q;
+    neg1 ^= flip;
+    neg2 = flip;
   }
 };
 
@@ -349,15 +444,16 @@ __global__ void __launch_bounds__(1024) k_msm_digits_glv(const uint32_t* __restr
 #pragma unroll
     for (int j = 0; j < 4; j++) k64[j] = (uint64_t)k.w[2 * j] | ((uint64_t)k.w[2 * j + 1] << 32);
     unsigned __int128 k1, k2;
-    uint32_t neg2;
-    Glv<C>::split(k64, k1, k2, neg2);
+    uint32_t neg1 = 0, neg2;
+    if constexpr (Glv<C>::signed_k1) Glv<C>::split(k64, k1, neg1, k2, neg2);
+    else Glv<C>::split(k64, k1, k2, neg2);
     FeG<Fr> m1, m2;
 #pragma unroll
     for (int j = 0; j < Fr::NG; j++) {
       m1.w[j] = j < 4 ? (uint32_t)(k1 >> (32 * j)) : 0u;
       m2.w[j] = j < 4 ? (uint32_t)(k2 >> (32 * j)) : 0u;
     }
-    emit_digits<Fr>(m1, 0u, i, g, dig, dg_lds);
+    emit_digits<Fr>(m1, neg1, i, g, dig, dg_lds);
     emit_digits<Fr>(m2, neg2, n0 + i, g, dig, dg_lds);
   }
   __syncthreads();

@@ -91,6 +91,8 @@ __global__ void __launch_bounds__(NTT_TPB) k_ntt_pass(Fe<P>* __restrict__ data, 
                                                       const Fe<P>* __restrict__ pc) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   Fe<P>* X = reinterpret_cast<Fe<P>*>(smem_raw);   // [T][B]
+  // the largest product operand of this pass is < 4p, against a canonical twiddle
+  static_assert(4 <= P::HEADROOM, "radix-2 NTT pass: operand bound exceeds R' / p");
   constexpr int TPB = NTT_TPB;
   const int T = 1 << t;
   const int lgB = NTT_TILE_LOG - t;
@@ -118,7 +120,8 @@ __global__ void __launch_bounds__(NTT_TPB) k_ntt_pass(Fe<P>* __restrict__ data, 
     Fe<P> v = ld_fe(data, addr);
     if (pb) v = fe_sub(fe_mul(v, fe_to_internal(ld_fe(pb, addr))), ld_fe(pc, addr));
     if (pre) v = fe_mul(v, ld_tab(pre, addr));
-    // inter-pass twiddle, lazily reduced (< 2p; the DIT tile takes < 4p)
+    // times the inter-pass twiddle (canonical: k_gen_pass_tw ends in a reduced
+    // product); the product is left lazily reduced (< 2p; the DIT tile takes < 4p)
     if (DIT && lo > 0) v = fe_mul_lz(v, ld_tab(tw, ((size_t)j << lo) + L));
     X[j * B + ol] = v;
   }
@@ -280,7 +283,8 @@ __global__ void __launch_bounds__(NTT_TPB) k_ntt_pass(Fe<P>* __restrict__ data, 
 // Bounds: DIF round inputs < 2p, outputs < 2p (two of the four sums reduced),
 // except the s = 1 round, whose outputs (< 8p) go straight to the store; DIT
 // (Harvey) round inputs < 4p, outputs < 4p.  Intermediate DIT passes store
-// lazily reduced (< 4p < 2^256; the next pass multiplies on load).
+// lazily reduced: < 4p where 4p < 2^256 (BN254, BLS12-377), < 2p for the 255-bit
+// BLS12-381 Fr (see the store); the next pass multiplies on load.
 // ---------------------------------------------------------------------------
 // waves per SIMD the radix-4 pass is compiled for (1: the compiler's choice);
 // A/B builds override it with -DNTT_R4_WPE=4
@@ -325,9 +329,16 @@ GM_DEV Fe<P> ntt_tw(const Fe<P>* __restrict__ sub, int i) {
 #define NTT_BFLY_CHAIN 2
 #endif
 #define MUL(x, y) (CH ? fe_mul<P, false, NTT_BFLY_CHAIN>(x, y) : fe_mul_lz(x, y))
+// The bounds the rounds state, against the field's headroom floor(R' / p)
+// (field_constants.hpp): a representative below K p fits the limbs and, times a
+// canonical twiddle (< p: the tables are written by reduced products), gives a
+// lazy product below 2p exactly when K <= HEADROOM.  BLS12-381 Fr has the least:
+// 70, against 169 (BN254) and 438 (BLS12-377).
+#define NTT_BOUND(K, what) static_assert((K) <= P::HEADROOM, "NTT " what ": operand bound exceeds R' / p")
 // DIF radix-2 butterfly pair of one round: (u, v) -> (u + v, (u - v + Kp) w)
 template <class P, int CH>
 GM_DEV void r4_dif(Fe<P> (&e)[4], const Fe<P>& t1, const Fe<P>& t2, const Fe<P>& t3) {
+  NTT_BOUND(9, "DIF round");  // fe_sub_cf<5>(s0, s1) < 9p, the largest product operand
   // stage lm: (e0, e2) by w_2m^jj, (e1, e3) by w_2m^(jj+s); inputs < 2p
   const Fe<P> s0 = fe_add_lz(e[0], e[2]);                        // < 4p
   const Fe<P> d0 = MUL(fe_sub_cf<3>(e[0], e[2]), t1);      // < 2p
@@ -345,6 +356,7 @@ GM_DEV void r4_dif(Fe<P> (&e)[4], const Fe<P>& t1, const Fe<P>& t2, const Fe<P>&
 // the s = 1 DIF round (twiddles 1, w_4, 1): inputs < 2p, outputs < 8p
 template <class P, int CH>
 GM_DEV void r4_dif_w4(Fe<P> (&e)[4], const Fe<P>& w4) {
+  NTT_BOUND(8, "DIF w_4 round");  // outputs < 8p
   const Fe<P> s0 = fe_add_lz(e[0], e[2]);                        // < 4p
   const Fe<P> d0 = fe_sub_lz<2>(e[0], e[2]);                     // < 4p
   const Fe<P> s1 = fe_add_lz(e[1], e[3]);                        // < 4p
@@ -362,6 +374,7 @@ GM_DEV void r4_dif_w4(Fe<P> (&e)[4], const Fe<P>& w4) {
 // (64 p^2 < R' p).
 template <class P, int CH, int B>
 GM_DEV void r4_dif_grow(Fe<P> (&e)[4], const Fe<P>& t1, const Fe<P>& t2, const Fe<P>& t3) {
+  NTT_BOUND(4 * B + 1, "growing DIF round");  // fe_sub_cf<2B + 1>(s0, s1) < (4B + 1) p
   const Fe<P> s0 = fe_add_lz(e[0], e[2]);                        // < 2B p
   const Fe<P> d0 = MUL(fe_sub_cf<B + 1>(e[0], e[2]), t1);        // < 2p
   const Fe<P> s1 = fe_add_lz(e[1], e[3]);                        // < 2B p
@@ -374,6 +387,9 @@ GM_DEV void r4_dif_grow(Fe<P> (&e)[4], const Fe<P>& t1, const Fe<P>& t2, const F
 }
 template <class P, int CH, int B>
 GM_DEV void r4_dif_w4_grow(Fe<P> (&e)[4], const Fe<P>& w4) {
+  // outputs < 4B p (64p at t = 8) go into the store's product with the inter-pass
+  // twiddle, which is canonical (k_gen_pass_tw): 4B p^2 < R' p
+  NTT_BOUND(4 * B, "growing DIF w_4 round");
   const Fe<P> s0 = fe_add_lz(e[0], e[2]);                        // < 2B p
   const Fe<P> d0 = fe_sub_lz<B>(e[0], e[2]);                     // < 2B p
   const Fe<P> s1 = fe_add_lz(e[1], e[3]);                        // < 2B p
@@ -386,6 +402,7 @@ GM_DEV void r4_dif_w4_grow(Fe<P> (&e)[4], const Fe<P>& w4) {
 // DIT (Harvey) round: (u, v) -> (u + v w, u - v w + 2p); inputs < 4p, outputs < 4p
 template <class P, int CH>
 GM_DEV void r4_dit(Fe<P> (&e)[4], const Fe<P>& a, const Fe<P>& b, const Fe<P>& c) {
+  NTT_BOUND(5, "DIT round");  // fe_sub_cf<3>(e2, v3) < 5p
   // stage lm: (e0, e1), (e2, e3) by w_2m^jj
   fe_reduce_k<2>(e[0]);
   fe_reduce_k<2>(e[2]);
@@ -408,6 +425,7 @@ GM_DEV void r4_dit(Fe<P> (&e)[4], const Fe<P>& a, const Fe<P>& b, const Fe<P>& c
 // the s = 1 DIT round (twiddles 1, 1, w_4): inputs < 2p, outputs < 4p
 template <class P, int CH>
 GM_DEV void r4_dit_w4(Fe<P> (&e)[4], const Fe<P>& w4) {
+  NTT_BOUND(8, "DIT w_4 round");  // outputs < 8p before the reduction
   const Fe<P> s0 = fe_add_lz(e[0], e[1]);                        // < 4p
   const Fe<P> s1 = fe_sub_lz<2>(e[0], e[1]);                     // < 4p
   const Fe<P> s2 = fe_add_lz(e[2], e[3]);                        // < 4p
@@ -425,6 +443,9 @@ GM_DEV void r4_dit_w4(Fe<P> (&e)[4], const Fe<P>& w4) {
 // with three subtractions per element instead of four per round.
 template <class P, int CH>
 GM_DEV void r4_dit_grow(Fe<P> (&e)[4], const Fe<P>& a, const Fe<P>& b, const Fe<P>& c) {
+  // inputs < 16p at the last round of t = 8 (8p, + 4p per round): s2 < 18p,
+  // fe_sub_cf<3>(e2, v3) < 19p; outputs < 20p, the store's product operand
+  NTT_BOUND(20, "growing DIT round");
   const Fe<P> v1 = MUL(e[1], a);                                 // < 2p
   const Fe<P> v3 = MUL(e[3], a);
   const Fe<P> s0 = fe_add_lz(e[0], v1);                          // < (B + 2) p
@@ -439,6 +460,7 @@ GM_DEV void r4_dit_grow(Fe<P> (&e)[4], const Fe<P>& a, const Fe<P>& b, const Fe<
 }
 template <class P, int CH>
 GM_DEV void r4_dit_w4_grow(Fe<P> (&e)[4], const Fe<P>& w4) {
+  NTT_BOUND(8, "growing DIT w_4 round");  // outputs < 8p
   const Fe<P> s0 = fe_add_lz(e[0], e[1]);                        // < 4p
   const Fe<P> s1 = fe_sub_lz<2>(e[0], e[1]);                     // < 4p
   const Fe<P> s2 = fe_add_lz(e[2], e[3]);                        // < 4p
@@ -450,6 +472,7 @@ GM_DEV void r4_dit_w4_grow(Fe<P> (&e)[4], const Fe<P>& w4) {
 }
 
 #undef MUL
+#undef NTT_BOUND
 
 // twiddles of a round whose lower stage is ls: w_4 for ls = 0, else DIF
 // (t1, t2, t3) / DIT (a, b, c) of the thread's group k
@@ -479,6 +502,11 @@ __global__ void __launch_bounds__(NTT_TPB) __attribute__((amdgpu_waves_per_eu(DI
                                                        const Fe<P>* __restrict__ pc) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   Fe<P>* X = reinterpret_cast<Fe<P>*>(smem_raw);  // [T][B]
+  // growing rounds: the switch below instantiates B up to 16 (DIF w_4) for
+  // t <= NTT_TMAX = 8; values stored between passes are below 2p (DIF) or 4p / 2p
+  // (DIT, see the store) and must fit the NG gnark words they are packed into
+  static_assert(NTT_TMAX <= 8, "r4_dif_w4_grow<16> / r4_dif_grow<8> cover t <= 8");
+  static_assert(P::BITS + 1 <= 32 * P::NG, "a value below 2p is stored in the element's gnark words");
   const int T = 1 << t;
   const int lgB = NTT_TILE_LOG - t;
   const int B = 1 << lgB;
@@ -648,7 +676,10 @@ __global__ void __launch_bounds__(NTT_TPB) __attribute__((amdgpu_waves_per_eu(DI
     } else if (post) {
       v = fe_mul<P, true, CH>(v, ld_tab(post, addr));  // inputs < 20p: (20p) p < R' p, output canonical
     } else if (DIT && !last_pass) {
-      // lazily reduced (< 4p < 2^256): the next DIT pass multiplies it on load
+      // lazily reduced (< 4p < 2^256): the next DIT pass multiplies it on load.
+      // BLS12-381 Fr (255 bits): 4p > 2^256 would lose its top bit in the
+      // element's eight words, so that field stores < 2p (2p < 2^256).
+      if constexpr (P::BITS + 2 > 32 * P::NG) fe_reduce_k<2>(v);
     } else {
       if (wide) fe_reduce_k<4>(v);
       fe_reduce_k<2>(v);
@@ -1279,18 +1310,20 @@ int ntt_root(int logn, void* w_host) {
   template int ntt_brev_roots<C>(gm_ctx*, size_t, const void**);
 GM_NTT_INST(CurveBN254)
 GM_NTT_INST(CurveBLS12377)
+GM_NTT_INST(CurveBLS12381)
 
 void ntt_domains_free(gm_ctx* ctx) {
   for (auto& kv : ctx->ntt_domains) {
-    const int curve = kv.first / 64;
-    auto free_all = [&](auto* d) {
-      for (void* p : d->allocs) hipFree(p);
-      delete d;
-    };
-    if (curve == 0)
-      free_all(reinterpret_cast<NttDomain<CurveBN254>*>(kv.second));
-    else
-      free_all(reinterpret_cast<NttDomain<CurveBLS12377>*>(kv.second));
+    // the key is C::id * 64 + logn (get_domain)
+    with_curve(
+        kv.first / 64,
+        [&](auto tag_) {
+          auto* d = reinterpret_cast<NttDomain<typename decltype(tag_)::type>*>(kv.second);
+          for (void* p : d->allocs) hipFree(p);
+          delete d;
+          return 0;
+        },
+        0);
   }
   ctx->ntt_domains.clear();
 }

@@ -55,6 +55,8 @@ GM_DEV Fe<P> fe_select(bool c, const Fe<P>& a, const Fe<P>& b) {
 template <class P, int BETA, bool CH = false>
 GM_DEV Fe<P> pf2_mul(const Fe<P>& a, const Fe<P>& b) {
   static_assert(BETA == -1 || BETA == -5, "unsupported non-residue");
+  // inputs < 4p: a b + (5p - ap)(|BETA| bp) < (16 + 20 |BETA|) p^2
+  GM_LAZY_BOUND(P, 16 + 20 * (BETA == -1 ? 1 : 5), "pf2_mul");
   const bool odd = pair_odd();
   const Fe<P> ap = fe_swap(a), bp = fe_swap(b);
   Fe<P> y2 = odd ? b : bp;
@@ -74,6 +76,7 @@ GM_DEV Fe<P> fe_mul4_redc(const Fe<P>& x1, const Fe<P>& y1, const Fe<P>& x2, con
                           const Fe<P>& y3, const Fe<P>& x4, const Fe<P>& y4) {
   constexpr int N = P::N;
   static_assert(N <= 9, "signed column bound needs N <= 9");
+  GM_LAZY_BOUND(P, 20, "fe_mul4_redc: the negative products must stay below p R'");
   uint32_t m[N];
   Fe<P> r;
   uint64_t acc = 0;
@@ -126,6 +129,7 @@ template <class P, int BETA, int IN, bool CH = false>
 GM_DEV Fe<P> pf2_sqr(const Fe<P>& a) {
   if constexpr (BETA == -1) {
     static_assert(IN <= 4, "pf2_sqr output bound (< 2p) needs inputs < 4p");
+    GM_LAZY_BOUND(P, 4 * IN * IN, "pf2_sqr: (a0 + a1)(a0 - a1 + IN p), both < 2 IN p");
     // lane 0: (a0 + a1)(a0 - a1);  lane 1: 2 a1 a0
     const bool odd = pair_odd();
     const Fe<P> ap = fe_swap(a);
@@ -193,7 +197,8 @@ GM_DEV PXYZZ<P> pxyzz_dbl_aff(const Fe<P>& px, const Fe<P>& py) {
 // CH: one mad chain per product (fe_mul CHAIN) in the add's products
 template <class P, int BETA, bool CH = false>
 GM_DEV void pxyzz_add_aff(PXYZZ<P>& a, const Fe<P>& px, const Fe<P>& py_in, bool neg) {
-  static_assert(P::BITS + 7 <= RADIX * P::N, "lazy reduction needs R' > 128 p");
+  // every product operand below 4p per component: pf2_mul, pf2_sqr<4> and fe_mul4_redc assert their bounds
+  GM_LAZY_BOUND(P, 64, "lane-pair mixed add: pf2_sqr<4>");
   constexpr bool TRIM = P::N <= 9;
   if (pair_all(fe_is_zero(px) && fe_is_zero(py_in))) return;
   Fe<P> py = py_in;

@@ -312,7 +312,7 @@ extern "C" {
 
 int gm_g16_pk_upload_dump_shard(gm_ctx* ctx, int curve, const gm_g16_pk_host* meta, int fd, uint64_t offset,
                                 unsigned flags, int rank, int world, uint64_t* end_offset, gm_g16_pk** out) {
-  if (int rc = check_curve_id(curve)) return rc;
+  if (int rc = check_curve_id(curve, "gm_g16_pk_upload_dump_shard")) return rc;
   if (!ctx || !meta || !out || fd < 0 || meta->domain_size < 2) return GM_ERR_INVALID;
   if (flags & ~(unsigned)(GM_PK_PRECOMPUTE | GM_PK_PRECOMPUTE_AUTO)) {
     set_error("pk dump: unknown flags");
@@ -369,6 +369,7 @@ int gm_g16_pk_upload_dump(gm_ctx* ctx, int curve, const gm_g16_pk_host* meta, in
 
 int gm_g16_pk_save_cache(gm_ctx* ctx, const gm_g16_pk* pk, int fd) {
   if (!ctx || !pk || fd < 0) return GM_ERR_INVALID;
+  if (int rc = check_curve_id(pk->curve, "gm_g16_pk_save_cache")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
   CacheHeader h;
@@ -430,7 +431,7 @@ int gm_g16_pk_load_cache(gm_ctx* ctx, int fd, gm_g16_pk** out) {
     set_error("pk cache: written by a build with another device point layout");
     return GM_ERR_INVALID;
   }
-  if ((rc = check_curve_id((int)h.curve))) return rc;
+  if ((rc = check_curve_id((int)h.curve, "gm_g16_pk_load_cache"))) return rc;
   if ((rc = check_cache_header(h))) return rc;
   auto* pk = new gm_g16_pk();
   auto fail = [&](int code) {
@@ -545,6 +546,7 @@ extern "C" {
 
 int gm_g16_stage_begin(gm_ctx* ctx, gm_g16_pk* pk, size_t nb_constraints, gm_g16_stage** out) {
   if (!ctx || !pk || !out) return GM_ERR_INVALID;
+  if (int rc = check_curve_id(pk->curve, "gm_g16_stage_begin")) return rc;
   if (nb_constraints > pk->n) {
     set_error("stage: more constraints than the domain size");
     return GM_ERR_INVALID;

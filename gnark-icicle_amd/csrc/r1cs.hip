@@ -106,7 +106,7 @@ extern "C" {
 int gm_r1cs_upload(gm_ctx* ctx, int curve, size_t nb_constraints, size_t nb_wires, const uint32_t* const* rowptr,
                    const uint32_t* const* cid, const uint32_t* const* vid, const void* coeffs, size_t ncoeffs,
                    gm_r1cs** out) {
-  if (int rc = check_curve_id(curve)) return rc;
+  if (int rc = check_curve_id(curve, "gm_r1cs_upload")) return rc;
   if (!ctx || !rowptr || !cid || !vid || !out || (ncoeffs && !coeffs)) return GM_ERR_INVALID;
   if (nb_constraints >= (size_t(1) << 31) || nb_wires >= (size_t(1) << 32) - 1 || ncoeffs < 2) {
     set_error("r1cs upload: sizes out of range (CoeffTable holds at least zero and one)");

@@ -367,7 +367,9 @@ static bool raw_field_valid(bool fr, int N, int fam, int K, int chain) {
     default: return false;
   }
 }
-template <class P, int BETA>
+// FR: a scalar field -- the Fp2 families are not compiled for it (their bounds are
+// asserted against the base field's headroom, which an Fr need not meet)
+template <class P, int BETA, bool FR>
 static int field_raw_t(gm_ctx* ctx, bool fr, int fam, int K, int chain, const void* a, const void* b, const void* c,
                        const void* d, void* out, size_t n) {
   if (!raw_field_valid(fr, P::N, fam, K, chain)) return GM_ERR_INVALID;
@@ -376,10 +378,15 @@ static int field_raw_t(gm_ctx* ctx, bool fr, int fam, int K, int chain, const vo
   const dim3 t(64), g(blocks_for(n, 64)), g2(blocks_for(2 * n, 64));
   hipStream_t s = ctx->stream;
   if (fam == GM_TRAW_FE2_MUL || fam == GM_TRAW_FE2_SQR || fam == GM_TRAW_MUL4_REDC) {
-    hipLaunchKernelGGL((k_field_raw_fe2<P, BETA>), g, t, 0, s, fam, A, B, C, D, O, n);
+    if constexpr (!FR) hipLaunchKernelGGL((k_field_raw_fe2<P, BETA>), g, t, 0, s, fam, A, B, C, D, O, n);
+    else return GM_ERR_INVALID;
   } else if (fam >= GM_TRAW_PF2_MUL) {
-    if (chain) hipLaunchKernelGGL((k_field_raw_pair<P, BETA, true>), g2, t, 0, s, fam, K, A, B, C, D, O, n);
-    else hipLaunchKernelGGL((k_field_raw_pair<P, BETA, false>), g2, t, 0, s, fam, K, A, B, C, D, O, n);
+    if constexpr (!FR) {
+      if (chain) hipLaunchKernelGGL((k_field_raw_pair<P, BETA, true>), g2, t, 0, s, fam, K, A, B, C, D, O, n);
+      else hipLaunchKernelGGL((k_field_raw_pair<P, BETA, false>), g2, t, 0, s, fam, K, A, B, C, D, O, n);
+    } else {
+      return GM_ERR_INVALID;
+    }
   } else {
     const bool chained = fam <= GM_TRAW_MUL2_NEGK || fam == GM_TRAW_SUB_CF_MUL;
     const int ch = chained ? chain : 0;
@@ -429,25 +436,23 @@ extern "C" {
 int gm_test_field_raw_op(gm_ctx* ctx, int curve, int kind, int op, int chain, const void* a_dev, const void* b_dev,
                          const void* c_dev, const void* d_dev, void* out_dev, size_t n) {
   if (!ctx || !a_dev || !out_dev || n == 0 || op < 0 || (kind != 0 && kind != 1)) return GM_ERR_INVALID;
-  if (curve != GM_BN254 && curve != GM_BLS12_377) return GM_ERR_INVALID;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_test_field_raw_op")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
   const int fam = op / 100, K = op % 100;
-  if (curve == GM_BN254)
-    return kind == 0 ? field_raw_t<Bn254Fr, -1>(ctx, true, fam, K, chain, a_dev, b_dev, c_dev, d_dev, out_dev, n)
-                     : field_raw_t<Bn254Fp, -1>(ctx, false, fam, K, chain, a_dev, b_dev, c_dev, d_dev, out_dev, n);
-  return kind == 0 ? field_raw_t<Bls377Fr, -5>(ctx, true, fam, K, chain, a_dev, b_dev, c_dev, d_dev, out_dev, n)
-                   : field_raw_t<Bls377Fp, -5>(ctx, false, fam, K, chain, a_dev, b_dev, c_dev, d_dev, out_dev, n);
+  return GM_CURVE(curve, kind == 0 ? field_raw_t<typename C::Fr, Fp2Beta<C>::value, true>(ctx, true, fam, K, chain, a_dev,
+                                                                                    b_dev, c_dev, d_dev, out_dev, n)
+                                   : field_raw_t<typename C::Fp, Fp2Beta<C>::value, false>(ctx, false, fam, K, chain, a_dev,
+                                                                                    b_dev, c_dev, d_dev, out_dev, n));
 }
 int gm_test_point_raw_op(gm_ctx* ctx, int curve, int g2, int op, int chain, const void* acc_in_dev,
                          const void* other_dev, const void* flags_dev, void* acc_out_dev, size_t n) {
   if (!ctx || !acc_in_dev || !acc_out_dev || n == 0) return GM_ERR_INVALID;
-  if (curve != GM_BN254 && curve != GM_BLS12_377) return GM_ERR_INVALID;
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_test_point_raw_op")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  return curve == GM_BN254
-             ? point_raw_t<Bn254Fp, -1>(ctx, g2, op, chain, acc_in_dev, other_dev, flags_dev, acc_out_dev, n)
-             : point_raw_t<Bls377Fp, -5>(ctx, g2, op, chain, acc_in_dev, other_dev, flags_dev, acc_out_dev, n);
+  return GM_CURVE(curve, point_raw_t<typename C::Fp, Fp2Beta<C>::value>(ctx, g2, op, chain, acc_in_dev, other_dev,
+                                                                        flags_dev, acc_out_dev, n));
 }
 }
 
@@ -478,21 +483,19 @@ static int point_op_t(gm_ctx* ctx, int op, const void* a, const void* b, void* o
 extern "C" {
 int gm_test_field_op(gm_ctx* ctx, int curve, int kind, int op, const void* a_dev, const void* b_dev,
                      void* out_dev, size_t n) {
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_test_field_op")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
   if (kind < 0 || kind > 2) return GM_ERR_INVALID;
-  return curve == GM_BN254 ? field_op_t<CurveBN254>(ctx, kind, op, a_dev, b_dev, out_dev, n)
-                           : field_op_t<CurveBLS12377>(ctx, kind, op, a_dev, b_dev, out_dev, n);
+  return GM_CURVE(curve, field_op_t<C>(ctx, kind, op, a_dev, b_dev, out_dev, n));
 }
 int gm_test_point_op(gm_ctx* ctx, int curve, int g2, int op, const void* a_dev, const void* b_dev,
                      void* out_dev, size_t n) {
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_test_point_op")) return rc;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  if (curve == GM_BN254)
-    return g2 ? point_op_t<CurveBN254, true>(ctx, op, a_dev, b_dev, out_dev, n)
-              : point_op_t<CurveBN254, false>(ctx, op, a_dev, b_dev, out_dev, n);
-  return g2 ? point_op_t<CurveBLS12377, true>(ctx, op, a_dev, b_dev, out_dev, n)
-            : point_op_t<CurveBLS12377, false>(ctx, op, a_dev, b_dev, out_dev, n);
+  return GM_CURVE(curve, g2 ? point_op_t<C, true>(ctx, op, a_dev, b_dev, out_dev, n)
+                            : point_op_t<C, false>(ctx, op, a_dev, b_dev, out_dev, n));
 }
 }
 
@@ -514,8 +517,7 @@ extern "C" int gm_test_msm_g2_keyless_plan(gm_ctx* ctx, int curve, const void* s
   if (!ctx || !scalars_dev || !points_dev || n == 0) return GM_ERR_INVALID;
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
-  return curve == GM_BN254 ? g2_keyless_plan_t<CurveBN254>(ctx, scalars_dev, points_dev, n)
-                           : g2_keyless_plan_t<CurveBLS12377>(ctx, scalars_dev, points_dev, n);
+  return GM_CURVE(curve, g2_keyless_plan_t<C>(ctx, scalars_dev, points_dev, n));
 }
 
 // The geometry of an MSM from the driver's own host functions (msm.hpp): no
@@ -582,7 +584,7 @@ static int msm_geometry_t(size_t n, int c_override, int layout, int curve, gm_te
 
 extern "C" int gm_test_msm_geometry(int curve, int g2, size_t n, int c_override, int layout, gm_test_msm_geom* out) {
   if (!out || n == 0 || layout < GM_TGEOM_PLAIN || layout > GM_TGEOM_DEFAULT ||
-      (curve != GM_BN254 && curve != GM_BLS12_377)) {
+      curve < 0 || curve >= CURVE_COUNT) {
     set_error("msm geometry: bad curve, size or layout");
     return GM_ERR_INVALID;
   }
@@ -591,11 +593,8 @@ extern "C" int gm_test_msm_geometry(int curve, int g2, size_t n, int c_override,
     set_error("msm geometry: window must be 0 (auto) or in [2, 24]");
     return GM_ERR_INVALID;
   }
-  if (curve == GM_BN254)
-    return g2 ? msm_geometry_t<CurveBN254, true>(n, c_override, layout, curve, out)
-              : msm_geometry_t<CurveBN254, false>(n, c_override, layout, curve, out);
-  return g2 ? msm_geometry_t<CurveBLS12377, true>(n, c_override, layout, curve, out)
-            : msm_geometry_t<CurveBLS12377, false>(n, c_override, layout, curve, out);
+  return GM_CURVE(curve, g2 ? msm_geometry_t<C, true>(n, c_override, layout, curve, out)
+                            : msm_geometry_t<C, false>(n, c_override, layout, curve, out));
 }
 
 /* The solver-side cost of staging the reference benchmark circuit's level shape

@@ -32,9 +32,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # GNARK_MI355X_LIB: an alternative build of the same library (same-box A/B runs)
 LIB_PATH = os.environ.get("GNARK_MI355X_LIB") or os.path.join(HERE, "libgnark_mi355x.so")
 
-BN254, BLS12_377 = 0, 1
-CURVES = {"bn254": BN254, "bls12377": BLS12_377}
-FP_BYTES = {BN254: 32, BLS12_377: 48}
+BN254, BLS12_377, BLS12_381 = 0, 1, 2
+CURVES = {"bn254": BN254, "bls12377": BLS12_377, "bls12381": BLS12_381}
+FP_BYTES = {BN254: 32, BLS12_377: 48, BLS12_381: 48}
 FR_BYTES = 32
 
 # exported symbols (include/gnark_mi355x.h) -- checked by tests/test_capi_symbols.py
@@ -938,7 +938,8 @@ def _mont_one(curve, g2: bool) -> np.ndarray:
     if key not in _MONT_ONE_CACHE:
         cid = curve_id(curve)
         p = {BN254: 21888242871839275222246405745257275088696311157297823662689037894645226208583,
-             BLS12_377: 258664426012969094010652733694893533536393512754914660539884262666720468348340822774968888139573360124440321458177}[cid]
+             BLS12_377: 258664426012969094010652733694893533536393512754914660539884262666720468348340822774968888139573360124440321458177,
+             BLS12_381: 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab}[cid]
         nb = FP_BYTES[cid]
         r = (1 << (8 * nb)) % p
         v = np.frombuffer(r.to_bytes(nb, "little"), np.uint8)
@@ -1064,8 +1065,13 @@ class ProvingKey:
         handle = ctypes.c_void_p()
         flags = self._flags(precompute)
         rank, world = shard if shard is not None else (0, 1)
-        _check(load_library().gm_g16_pk_upload_shard(ctx.handle, self.curve, ctypes.byref(h), flags, rank, world,
-                                                     ctypes.byref(handle)))
+        if shard is None:
+            # the whole key: the entry every curve serves (a rank's share is BN254 / BLS12-377 only)
+            _check(load_library().gm_g16_pk_upload_ex(ctx.handle, self.curve, ctypes.byref(h), flags,
+                                                      ctypes.byref(handle)))
+        else:
+            _check(load_library().gm_g16_pk_upload_shard(ctx.handle, self.curve, ctypes.byref(h), flags, rank,
+                                                         world, ctypes.byref(handle)))
         self.handle = handle
         self.n, self.nb_wires, self.nb_public = domain_size, nb_wires, nb_public
         self.shard = (rank, world)

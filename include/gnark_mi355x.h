@@ -39,7 +39,19 @@ typedef enum {
   GM_ERR_UNSUPPORTED = -4, /* curve/group combination not built */
 } gm_status;
 
-typedef enum { GM_BN254 = 0, GM_BLS12_377 = 1 } gm_curve;
+/* Curve ids.  BN254 and BLS12-377 are served by every entry that takes a curve.
+ * BLS12-381 (Fp 381 bits = 6 x u64, Fr 255 bits = 4 x u64, G1 96 B, G2 192 B) is
+ * served by the host group helpers, the point uploads, every MSM entry, the NTT /
+ * poly-ops / computeH calls, the KZG commit / open calls and the Groth16 key
+ * upload and prover (gm_g16_pk_upload[_ex], gm_g16_prove[_device], gm_g16_finish,
+ * gm_g16_partial_bytes).  Every other entry that takes a curve -- the PLONK calls
+ * and gm_kzg_srs_lagrange, gm_r1cs_upload and what needs it (gm_g16_prove_r1cs,
+ * gm_g16_setup*, gm_g16_pk_setup), gm_batch_mul_fixed / gm_batch_mul_base, the
+ * key dump / cache loaders, gm_g16_pk_upload_shard / _multi, gm_g16_prove_partial,
+ * the staged-input calls and gm_icicle_* -- answers GM_ERR_UNSUPPORTED for it,
+ * before any allocation, upload or launch, with a message that names the curve
+ * and the entry.  Any other id is GM_ERR_INVALID, "unknown curve id". */
+typedef enum { GM_BN254 = 0, GM_BLS12_377 = 1, GM_BLS12_381 = 2 } gm_curve;
 
 typedef struct gm_ctx gm_ctx;
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate the Montgomery constants for the four prime fields on the hot path.
+"""Generate the Montgomery constants for the six prime fields on the hot path.
 
 Fields (gnark-crypto memory layout: little-endian 64-bit limbs, Montgomery form
 x*R mod p with R = 2^(64*limbs)):
@@ -8,12 +8,16 @@ x*R mod p with R = 2^(64*limbs)):
   bn254.fr      254-bit, 4 x u64
   bls12377.fp   377-bit, 6 x u64
   bls12377.fr   253-bit, 4 x u64
+  bls12381.fp   381-bit, 6 x u64
+  bls12381.fr   255-bit, 4 x u64
 
 Writes two independent headers so that the product (device + host code) and
 the test oracle never share a source file:
 
   gnark-icicle_amd/csrc/field_constants.hpp   (product)
-  oracle/oracle_constants.h                   (test oracle)
+  oracle/oracle_constants.h                   (test oracle; BN254 and BLS12-377
+                                               only: the C++ oracle does not know
+                                               BLS12-381, whose reference is pyref)
 
 Run:  python tools/gen_field_constants.py
 """
@@ -26,7 +30,12 @@ FIELDS = {
     "BN254_FR": (21888242871839275222246405745257275088548364400416034343698204186575808495617, 4),
     "BLS12377_FP": (258664426012969094010652733694893533536393512754914660539884262666720468348340822774968888139573360124440321458177, 6),
     "BLS12377_FR": (8444461749428370424248824938781546531375899335154063827935233455917409239041, 4),
+    "BLS12381_FP": (0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab, 6),
+    "BLS12381_FR": (0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001, 4),
 }
+# the fields and generators the test oracle's header carries (never extended)
+ORACLE_FIELDS = ("BN254_FP", "BN254_FR", "BLS12377_FP", "BLS12377_FR")
+ORACLE_GENERATORS = ("BN254_G1", "BN254_G2", "BLS12377_G1", "BLS12377_G2")
 
 
 # curve generators, canonical coordinates (gnark-crypto curve.Generators())
@@ -45,6 +54,14 @@ GENERATORS = {
         140913150380207355837477652521042157274541796891053068589147167627541651775299824604154852141315666357241556069118,
         63160294768292073209381361943935198908131692476676907196754037919244929611450776219210369229519898517858833747423,
         149157405641012693445398062341192467754805999074082136895788947234480009303640899064710353187729182149407503257491]),
+    "BLS12381_G1": (("BLS12381_FP", 6), [
+        0x17f1d3a73197d7942695638c4fa9ac0fc3688c4f9774b905a14e3a3f171bac586c55e83ff97a1aeffb3af00adb22c6bb,
+        0x08b3f481e3aaa0f1a09e30ed741d8ae4fcf5e095d5d00af600db18cb2c04b3edd03cc744a2888ae40caa232946c5e7e1]),
+    "BLS12381_G2": (("BLS12381_FP", 6), [
+        0x024aa2b2f08f0a91260805272dc51051c6e47ad4fa403b02b4510b647ae3d1770bac0326a805bbefd48056c8c121bdb8,
+        0x13e02b6052719f607dacd3a088274f65596bd0d09920b61ab5da61bbdc7f5049334cf11213945d57e5ac7d055d042b7e,
+        0x0ce5d527727d6e118cc9cdc6da2e351aadfd9baa8cbdd3a76d429a695160d12c923ac9cc3baca289e193548608b82801,
+        0x0606c4a02ea734cc32acd2b02bc28b99cb3e287e85a763af267492ab572e99ab3f370d275cec1da1aaa9075ff05f79be]),
 }
 
 
@@ -84,7 +101,16 @@ def fmt_arr(vals, bits):
 # R' = 2^(29*N) > 4p and a FIPS column of 2N products of 58-bit terms fits in
 # 64 bits (2N * 2^58 < 2^64  <=>  N <= 31).
 RADIX = 29
-N29 = {"BN254_FP": 9, "BN254_FR": 9, "BLS12377_FP": 14, "BLS12377_FR": 9}
+N29 = {"BN254_FP": 9, "BN254_FR": 9, "BLS12377_FP": 14, "BLS12377_FR": 9,
+       "BLS12381_FP": 14, "BLS12381_FR": 9}
+
+
+def headroom(name):
+    """floor(R' / p): a lazily reduced product a b with a b < k p^2 stays below
+    R' p, and a representative below k p fits the limbs, exactly when
+    k <= headroom.  The kernels assert their stated bounds against it."""
+    p = FIELDS[name][0]
+    return (1 << (RADIX * N29[name])) // p
 
 
 def consts29(p, n64, n29):
@@ -124,6 +150,7 @@ def product_header():
         out.append("#define GM_%s_N29 %d" % (name, n29))
         out.append("#define GM_%s_NG %d" % (name, n32))
         out.append("#define GM_%s_INV29 0x%08xu" % (name, c29["inv"]))
+        out.append("#define GM_%s_HEADROOM %dull" % (name, headroom(name)))
         for key in ("p", "one", "r2", "kin", "kout", "kcan", "kgn"):
             out.append("#define GM_%s_%s29 {%s}" % (name, key.upper(), fmt_arr(limbs(c29[key], n29, RADIX), 32)))
         out.append("")
@@ -139,14 +166,15 @@ def oracle_header():
     out = ["/* Generated by tools/gen_field_constants.py -- do not edit.",
            " * TEST ORACLE ONLY: constants for the CPU restatement in oracle/. */",
            "#ifndef ORACLE_CONSTANTS_H", "#define ORACLE_CONSTANTS_H", "#include <stdint.h>", ""]
-    for name, (p, n64) in FIELDS.items():
+    for name in ORACLE_FIELDS:
+        p, n64 = FIELDS[name]
         c = consts(p, n64)
         out.append("#define O_%s_P {%s}" % (name, fmt_arr(limbs(p, n64, 64), 64)))
         out.append("#define O_%s_ONE {%s}" % (name, fmt_arr(limbs(c["one"], n64, 64), 64)))
         out.append("#define O_%s_R2 {%s}" % (name, fmt_arr(limbs(c["r2"], n64, 64), 64)))
         out.append("#define O_%s_INV 0x%016xull" % (name, c["inv64"]))
         out.append("")
-    for g in GENERATORS:
+    for g in ORACLE_GENERATORS:
         out.append("#define O_%s_GEN {%s}" % (g, fmt_arr(gen_mont_words(g), 64)))
     out.append("")
     out.append("#endif")
