@@ -18,6 +18,7 @@
 #include "plonk_pk.hpp"
 #include "plonk_session.hpp"
 #include "plonk_setup.hpp"
+#include "plonk_scs.hpp"
 #include "plonk_wires.hpp"
 #include "plonk_wires_perm.hpp"
 #include "msm.hpp"
@@ -196,6 +197,7 @@ int gm_destroy(gm_ctx* ctx) {
   while (!ctx->spare_keys.empty()) stage_spare_release(ctx->spare_keys.back());
   while (!ctx->plonk_spare_keys.empty()) plonk_spare_release(ctx->plonk_spare_keys.back());
   while (!ctx->plonk_wires.empty()) plonk_wires_release(ctx->plonk_wires.back());  // wire tables not freed
+  while (!ctx->plonk_scs.empty()) plonk_scs_release(ctx->plonk_scs.back());        // circuits not freed
   for (auto& pr : ctx->pending_reads) hipEventDestroy(pr.second);
   ctx->pending_reads.clear();
   ntt_domains_free(ctx);
@@ -1006,6 +1008,10 @@ int gm_plonk_wires_free(gm_ctx* ctx, gm_plonk_wires* w) {
     set_error("plonk wires free: the tables were uploaded on another context");
     return GM_ERR_INVALID;
   }
+  if (w->borrowed) {
+    set_error("plonk wires free: the tables belong to a circuit (gm_plonk_scs_free frees them)");
+    return GM_ERR_INVALID;
+  }
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
   GM_HIP(hipStreamSynchronize(ctx->stream));
@@ -1121,6 +1127,55 @@ int gm_plonk_pk_setup_wires(gm_ctx* ctx, int curve, const gm_plonk_setup_host* i
   if (int rc = check_curve(curve, CURVES_01, "gm_plonk_pk_setup_wires")) return rc;
   if (!ctx || !in || !w || !out) return refuse_null("plonk pk setup wires");
   return plonk_pk_setup_wires(ctx, curve, in, w, flags, out, vk_digests, srs_lagrange_out);
+}
+
+// ---- PLONK circuit on the device (plonk_scs.hip) --------------------------------------
+int gm_plonk_scs_upload(gm_ctx* ctx, int curve, const gm_plonk_scs_host* in, gm_plonk_scs** out) {
+  if (int rc = check_curve(curve, CURVES_01, "gm_plonk_scs_upload")) return rc;
+  if (!ctx || !in || !out) return refuse_null("plonk scs upload");
+  return plonk_scs_upload(ctx, curve, in, out);
+}
+
+int gm_plonk_scs_bytes(const gm_plonk_scs* scs, size_t* resident_bytes) {
+  if (!scs || !resident_bytes) return refuse_null("plonk scs bytes");
+  *resident_bytes = scs->bytes;
+  return GM_OK;
+}
+
+int gm_plonk_scs_free(gm_ctx* ctx, gm_plonk_scs* scs) {
+  if (!ctx || !scs) return refuse_null("plonk scs free");
+  if (scs->ctx != ctx) {
+    set_error("plonk scs free: the circuit was uploaded on another context");
+    return GM_ERR_INVALID;
+  }
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  GM_HIP(hipStreamSynchronize(ctx->stream));
+  plonk_scs_release(scs);
+  return GM_OK;
+}
+
+int gm_plonk_scs_wires(const gm_plonk_scs* scs, const gm_plonk_wires** out) {
+  if (!scs || !out) return refuse_null("plonk scs wires");
+  *out = &scs->wires;
+  return GM_OK;
+}
+
+int gm_plonk_scs_selector(gm_ctx* ctx, const gm_plonk_scs* scs, unsigned which, void* out_dev) {
+  if (!ctx || !scs || !out_dev) return refuse_null("plonk scs selector");
+  return plonk_scs_selector(ctx, scs, which, out_dev);
+}
+
+int gm_plonk_pk_setup_scs(gm_ctx* ctx, const gm_plonk_scs* scs, const void* srs_canonical, size_t srs_canonical_len,
+                          unsigned flags, gm_plonk_pk** out, void* vk_digests, void* srs_lagrange_out) {
+  if (!ctx || !scs || !out) return refuse_null("plonk pk setup scs");
+  return plonk_pk_setup_scs(ctx, scs, srs_canonical, srs_canonical_len, flags, out, vk_digests, srs_lagrange_out);
+}
+
+int gm_plonk_scs_check(gm_ctx* ctx, const gm_plonk_scs* scs, const void* witness_host, size_t* nb_unsatisfied,
+                       size_t* first_unsatisfied) {
+  if (!ctx || !scs || !witness_host || !nb_unsatisfied || !first_unsatisfied) return refuse_null("plonk scs check");
+  return plonk_scs_check(ctx, scs, witness_host, nb_unsatisfied, first_unsatisfied);
 }
 
 // ---- NTT --------------------------------------------------------------------------

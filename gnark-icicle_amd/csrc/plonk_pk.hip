@@ -71,11 +71,19 @@ int finish_t(gm_ctx* ctx, const PlonkPkFixed& f, unsigned flags, gm_plonk_pk* pk
   Arena arena(ctx);
   DevBuf tmp;
   if ((rc = tmp.alloc(arena, 32 * n))) return rc;
-  // Lagrange regular (at `lag`, or from the host through tmp; host == nullptr: it
-  // lies at `lag` already) -> canonical regular at dst; its digest while it is there
-  auto canonical = [&](const void* host, void* lag, void* dst, size_t digest) -> int {
+  // selector column `which` (GM_SCS_QL .. GM_SCS_QCP0 + j) at dst: the host
+  // vector, or what the key's generator makes of it on the device
+  auto column = [&](unsigned which, const void* host, void* dst) -> int {
+    if (f.gen) return f.gen->fill(ctx, f.gen->self, which, dst);
+    GM_HIP(hipMemcpyAsync(dst, host, 32 * n, hipMemcpyHostToDevice, ctx->stream));
+    return GM_OK;
+  };
+  // Lagrange regular (at `lag`, or column `which` through tmp; which < 0: it lies
+  // at `lag` already) -> canonical regular at dst; its digest while it is there
+  auto canonical = [&](int which, const void* host, void* lag, void* dst, size_t digest) -> int {
     void* src = lag ? lag : tmp.p;
-    if (host) GM_HIP(hipMemcpyAsync(src, host, 32 * n, hipMemcpyHostToDevice, ctx->stream));
+    if (which >= 0)
+      if (int r = column((unsigned)which, host, src)) return r;
     if (int r = bitrev_copy_device<C>(ctx, dst, src, n)) return r;
     if (int r = ntt_device<C>(ctx, dst, n, true, true, false)) return r;
     if (!vk_digests) return GM_OK;
@@ -85,13 +93,16 @@ int finish_t(gm_ctx* ctx, const PlonkPkFixed& f, unsigned flags, gm_plonk_pk* pk
   auto lag = [&](size_t k) { return const_cast<void*>(pk->lagrange(k)); };
   // the verifying key's order: S1 S2 S3 Ql Qr Qm Qo Qk Qcp_j
   const void* sel[4] = {f.ql, f.qr, f.qm, f.qo};
+  static_assert(GM_SCS_QL == 0 && GM_SCS_QO == 3 && GM_SCS_QK == 4 && GM_SCS_QCP0 == 5, "the columns' numbering");
   for (int k = 0; k < 4; k++)
-    if ((rc = canonical(sel[k], nullptr, can(gm_plonk_pk::QL + k), 3 + k))) return rc;
+    if ((rc = canonical(GM_SCS_QL + k, sel[k], nullptr, can(gm_plonk_pk::QL + k), 3 + k))) return rc;
   for (int k = 0; k < 3; k++)
-    if ((rc = canonical(nullptr, lag(gm_plonk_pk::LAG_S1 + k), can(gm_plonk_pk::S1 + k), k))) return rc;
+    if ((rc = canonical(-1, nullptr, lag(gm_plonk_pk::LAG_S1 + k), can(gm_plonk_pk::S1 + k), k))) return rc;
   for (size_t j = 0; j < nb; j++)
-    if ((rc = canonical(f.qcp[j], nullptr, can(gm_plonk_pk::NCANON + j), 8 + j))) return rc;
-  GM_HIP(hipMemcpyAsync(lag(gm_plonk_pk::LAG_QK), f.qk, 32 * n, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = canonical((int)(GM_SCS_QCP0 + j), f.gen ? nullptr : f.qcp[j], nullptr, can(gm_plonk_pk::NCANON + j),
+                        8 + j)))
+      return rc;
+  if ((rc = column(GM_SCS_QK, f.qk, lag(gm_plonk_pk::LAG_QK)))) return rc;
   if (vk_digests)
     if ((rc = commit_affine<C>(ctx, lag(gm_plonk_pk::LAG_QK), pk->srs_lagrange, n, (char*)vk_digests + pb * 7)))
       return rc;
@@ -126,8 +137,10 @@ int plonk_pk_check(int curve, const PlonkPkFixed& f, unsigned flags, bool other_
     set_error("plonk pk: unknown flag");
     return GM_ERR_INVALID;
   }
-  for (const void* p : {f.ql, f.qr, f.qm, f.qo, f.qk, f.srs_canonical})
-    if (!p) other_null = true;
+  if (!f.srs_canonical) other_null = true;
+  if (!f.gen)
+    for (const void* p : {f.ql, f.qr, f.qm, f.qo, f.qk})
+      if (!p) other_null = true;
   if (other_null) {
     set_error("plonk pk: the polynomials and both SRSs must be non-null");
     return GM_ERR_INVALID;
@@ -140,12 +153,12 @@ int plonk_pk_check(int curve, const PlonkPkFixed& f, unsigned flags, bool other_
     set_error("plonk pk: more public inputs than rows");
     return GM_ERR_INVALID;
   }
-  if (nb > 1024 || (nb && (!f.qcp || !f.commitment_row))) {
+  if (nb > 1024 || (nb && ((!f.gen && !f.qcp) || !f.commitment_row))) {
     set_error("plonk pk: nb_bsb > 0 needs the qcp table and the commitment rows (at most 1024 gates)");
     return GM_ERR_INVALID;
   }
   for (size_t j = 0; j < nb; j++) {
-    if (!f.qcp[j]) {
+    if (!f.gen && !f.qcp[j]) {
       set_error("plonk pk: a qcp entry is null");
       return GM_ERR_INVALID;
     }

@@ -45,6 +45,13 @@ struct gm_plonk_pk {
 namespace gm {
 // What both ways of making a key are given (gm_plonk_pk_host and
 // gm_plonk_setup_host share these members): the key's fixed part.
+// A selector column that is made on the device instead of copied from the
+// host: fill queues column `which` (GM_SCS_QL .. GM_SCS_QCP0 + j), n elements,
+// Lagrange regular, at out_dev on ctx->stream.
+struct PlonkColumnGen {
+  int (*fill)(gm_ctx* ctx, const void* self, unsigned which, void* out_dev);
+  const void* self;
+};
 struct PlonkPkFixed {
   size_t n, nb_public;
   const void *ql, *qr, *qm, *qo, *qk;
@@ -53,6 +60,9 @@ struct PlonkPkFixed {
   const size_t* commitment_row;
   const void* srs_canonical;
   size_t srs_canonical_len;
+  // the columns' source: nullptr = the host vectors above; otherwise those (and
+  // qcp) are not read
+  const PlonkColumnGen* gen = nullptr;
 };
 // Every argument is checked on the host before the first device call.
 int plonk_pk_upload(gm_ctx* ctx, int curve, const gm_plonk_pk_host* host, unsigned flags, gm_plonk_pk** out);

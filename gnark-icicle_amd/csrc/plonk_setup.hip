@@ -42,6 +42,7 @@
 #include "msm.hpp"
 #include "ntt.hpp"
 #include "plonk_pk.hpp"
+#include "plonk_scs.hpp"
 #include "plonk_setup.hpp"
 #include "plonk_wires_perm.hpp"
 #include "runtime.hpp"
@@ -422,6 +423,28 @@ int plonk_pk_setup_wires(gm_ctx* ctx, int curve, const gm_plonk_setup_host* in, 
     return refuse("the wire tables have n = " + std::to_string(w->n) + ", the key has n = " + std::to_string(in->n));
   if (w->n > WIRES_PERM_MAX_N) return refuse("the permutation from the wire tables needs n <= 2^30");
   return pk_setup_run(ctx, curve, in, w, f, flags, out, vk_digests, srs_lagrange_out);
+}
+
+// The _wires call with nothing dense from the host: sizes, commitment rows and
+// tables from the circuit, every selector made by its kernel into the column
+// where plonk_pk_finish would copy the host vector.
+int plonk_pk_setup_scs(gm_ctx* ctx, const gm_plonk_scs* s, const void* srs_canonical, size_t srs_canonical_len,
+                       unsigned flags, gm_plonk_pk** out, void* vk_digests, void* srs_lagrange_out) {
+  const PlonkColumnGen gen = {plonk_scs_column, s};
+  gm_plonk_setup_host in = {};
+  in.n = s->n;
+  in.nb_public = s->nb_public;
+  in.nb_bsb = s->nb_bsb;
+  in.commitment_row = s->commitment_row.data();
+  in.srs_canonical = srs_canonical;
+  in.srs_canonical_len = srs_canonical_len;
+  const PlonkPkFixed f = {in.n,      in.nb_public, nullptr, nullptr, nullptr, nullptr, nullptr,
+                          in.nb_bsb, nullptr,      in.commitment_row, in.srs_canonical, in.srs_canonical_len, &gen};
+  if (int rc = plonk_pk_check(s->curve, f, flags, false)) return rc;
+  if (!vk_digests) return refuse("vk_digests must be non-null");
+  if (s->ctx != ctx) return refuse("the circuit was uploaded on another context");
+  if (s->n > WIRES_PERM_MAX_N) return refuse("the permutation from the wire tables needs n <= 2^30");
+  return pk_setup_run(ctx, s->curve, &in, &s->wires, f, flags, out, vk_digests, srs_lagrange_out);
 }
 
 #define GM_SETUP_INST(C)                                                                     \

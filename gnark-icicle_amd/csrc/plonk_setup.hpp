@@ -32,4 +32,8 @@ int plonk_pk_setup(gm_ctx* ctx, int curve, const gm_plonk_setup_host* in, unsign
 // plonk_pk_setup with the permutation taken from w (in->permutation is NULL)
 int plonk_pk_setup_wires(gm_ctx* ctx, int curve, const gm_plonk_setup_host* in, const gm_plonk_wires* w,
                          unsigned flags, gm_plonk_pk** out, void* vk_digests, void* srs_lagrange_out);
+// plonk_pk_setup_wires from a resident circuit (plonk_scs.hip): its tables, its
+// sizes and commitment rows, its selectors generated on the device
+int plonk_pk_setup_scs(gm_ctx* ctx, const gm_plonk_scs* s, const void* srs_canonical, size_t srs_canonical_len,
+                       unsigned flags, gm_plonk_pk** out, void* vk_digests, void* srs_lagrange_out);
 }  // namespace gm

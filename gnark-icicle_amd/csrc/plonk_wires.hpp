@@ -10,6 +10,9 @@ struct gm_plonk_wires {
   gm_ctx* ctx = nullptr;
   size_t n = 0, nb_wires = 0;
   uint32_t* tab = nullptr;  // one allocation: xa, xb, xc, n ids each, every id < nb_wires
+  // the tables lie inside a gm_plonk_scs (plonk_scs.hpp), which frees them:
+  // gm_plonk_wires_free refuses the object, and it is on no context's list
+  bool borrowed = false;
 };
 
 namespace gm {

@@ -145,6 +145,9 @@ struct gm_ctx {
   // PLONK wire tables uploaded on this context (gm_plonk_wires_upload) and not yet
   // freed: gm_destroy releases them
   std::vector<gm_plonk_wires*> plonk_wires;
+  // PLONK circuits uploaded on this context (gm_plonk_scs_upload) and not yet
+  // freed: gm_destroy releases them, their borrowed wire tables with them
+  std::vector<gm_plonk_scs*> plonk_scs;
 };
 
 namespace gm {

@@ -62,6 +62,8 @@ SYMBOLS = [
     "gm_plonk_session_round1_witness", "gm_plonk_session_bsb22_sparse",
     "gm_kzg_srs_lagrange", "gm_plonk_sigma", "gm_plonk_pk_setup",
     "gm_plonk_wires_permutation", "gm_plonk_sigma_wires", "gm_plonk_pk_setup_wires",
+    "gm_plonk_scs_upload", "gm_plonk_scs_bytes", "gm_plonk_scs_free", "gm_plonk_scs_wires",
+    "gm_plonk_scs_selector", "gm_plonk_pk_setup_scs", "gm_plonk_scs_check",
     "gm_set_fixed_base_window", "gm_batch_mul_fixed",
     "gm_set_g16_setup_column_cut", "gm_g16_setup_sizes", "gm_g16_setup", "gm_g16_pk_setup",
 ]
@@ -143,6 +145,21 @@ class _PlonkSetupHost(ctypes.Structure):
                    ("nb_bsb", ctypes.c_size_t), ("qcp", ctypes.POINTER(ctypes.c_void_p)),
                    ("commitment_row", ctypes.POINTER(ctypes.c_size_t)), ("srs_canonical", ctypes.c_void_p),
                    ("srs_canonical_len", ctypes.c_size_t)])
+
+
+class _PlonkScsHost(ctypes.Structure):
+    """gm_plonk_scs_host (include/gnark_mi355x.h)."""
+    _fields_ = [("n", ctypes.c_size_t), ("nb_public", ctypes.c_size_t), ("nb_constraints", ctypes.c_size_t),
+                ("nb_wires", ctypes.c_size_t), ("records", ctypes.POINTER(ctypes.c_uint32)),
+                ("coeffs", ctypes.c_void_p), ("ncoeffs", ctypes.c_size_t), ("nb_bsb", ctypes.c_size_t),
+                ("committed", ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32))),
+                ("committed_len", ctypes.POINTER(ctypes.c_size_t)),
+                ("commitment_index", ctypes.POINTER(ctypes.c_size_t))]
+
+
+# columns of gm_plonk_scs_selector; SCS_QCP0 + j is qcp_j
+SCS_QL, SCS_QR, SCS_QM, SCS_QO, SCS_QK, SCS_QCP0 = range(6)
+SCS_RECORD_WORDS = 9  # XA XB XC QL QR QO QM QC Commitment
 
 
 PLONK_ROUND1_FIELDS = ("l", "r", "o", "public_inputs", "commitment_vals", "bl", "br", "bo", "bz", "h_rand")
@@ -333,6 +350,13 @@ def load_library(path: str = LIB_PATH):
     L.gm_plonk_wires_permutation.argtypes = [vp, vp, vp]
     L.gm_plonk_sigma_wires.argtypes = [vp, i, vp, vp, vp, vp]
     L.gm_plonk_pk_setup_wires.argtypes = [vp, i, ctypes.POINTER(_PlonkSetupHost), vp, ctypes.c_uint, pvp, vp, vp]
+    L.gm_plonk_scs_upload.argtypes = [vp, i, ctypes.POINTER(_PlonkScsHost), pvp]
+    L.gm_plonk_scs_bytes.argtypes = [vp, psz]
+    L.gm_plonk_scs_free.argtypes = [vp, vp]
+    L.gm_plonk_scs_wires.argtypes = [vp, pvp]
+    L.gm_plonk_scs_selector.argtypes = [vp, vp, ctypes.c_uint, vp]
+    L.gm_plonk_pk_setup_scs.argtypes = [vp, vp, vp, sz, ctypes.c_uint, pvp, vp, vp]
+    L.gm_plonk_scs_check.argtypes = [vp, vp, vp, psz, psz]
     L.gm_set_fixed_base_window.argtypes = [vp, i]
     L.gm_batch_mul_fixed.argtypes = [vp, i, i, vp, vp, sz, vp]
     L.gm_set_g16_setup_column_cut.argtypes = [vp, i]
@@ -1393,6 +1417,30 @@ class PlonkProvingKey:
                          cache=cache, srs_canonical_len=srs_canonical_len, lagrange=lagrange, digests=digests,
                          wires=wires)
 
+    @classmethod
+    def setup_from_circuit(cls, circuit: "PlonkCircuit", srs_canonical, cache: bool = True,
+                           srs_canonical_len: int | None = None, lagrange: bool = False, digests: bool = True):
+        """The key from a resident circuit and the canonical SRS alone
+        (gm_plonk_pk_setup_scs); returns what setup() returns."""
+        self = cls.__new__(cls)
+        ctx, curve, n = circuit.ctx, circuit.curve, circuit.n
+        self.ctx, self.curve, self.n, self.nb_public = ctx, curve, n, circuit.nb_public
+        self.nb_bsb = circuit.nb_bsb
+        self.handle = None
+        can = _buf(srs_canonical) if srs_canonical is not None else None
+        pb = point_bytes(curve, False)
+        can_len = (can.size // pb if can is not None else 0) if srs_canonical_len is None else srs_canonical_len
+        dig = np.zeros(pb * (8 + self.nb_bsb), np.uint8) if digests else None
+        lag = np.zeros(pb * n, np.uint8) if lagrange else None
+        out = ctypes.c_void_p()
+        _check(load_library().gm_plonk_pk_setup_scs(
+            ctx.handle, circuit.handle, _p(can) if can is not None else None, can_len,
+            0 if cache else PLONK_PK_NO_COSET_CACHE, ctypes.byref(out), _p(dig) if digests else None,
+            _p(lag) if lagrange else None))
+        self.handle = out
+        db = dig.tobytes() if digests else b""
+        return self, [db[i:i + pb] for i in range(0, len(db), pb)], (lag.tobytes() if lagrange else None)
+
     def resident_bytes(self) -> tuple[int, int]:
         """(resident bytes, coset cache bytes) of gm_plonk_pk_bytes."""
         a, b = ctypes.c_size_t(), ctypes.c_size_t()
@@ -1546,6 +1594,88 @@ class PlonkWires:
     def free(self):
         if self.handle:
             _check(load_library().gm_plonk_wires_free(self.ctx.handle, self.handle))
+            self.handle = None
+
+
+class PlonkCircuit:
+    """A PLONK constraint system resident on the device (gm_plonk_scs_upload).
+    records: nb_constraints x 9 integers, gnark's SparseR1C as it lies in memory
+    (XA XB XC QL QR QO QM QC Commitment); coeffs: the CoeffTable as Montgomery
+    fr.Element bytes; committed: per BSB22 gate its constraint indices;
+    commitment_index: per gate the constraint of its commitment.  A None among
+    records / coeffs passes a NULL pointer; nb_constraints and ncoeffs override
+    the sizes taken from the arrays."""
+
+    def __init__(self, ctx: Context, curve, n: int, nb_public: int, nb_wires: int, records, coeffs, committed=(),
+                 commitment_index=(), nb_constraints: int | None = None, ncoeffs: int | None = None):
+        self.ctx, self.curve, self.n, self.nb_public, self.nb_wires = ctx, curve, n, nb_public, nb_wires
+        rec = np.ascontiguousarray(records, dtype=np.uint32).reshape(-1) if records is not None else None
+        co = _buf(coeffs) if coeffs is not None else None
+        h = _PlonkScsHost()
+        h.n, h.nb_public, h.nb_wires = n, nb_public, nb_wires
+        h.nb_constraints = (rec.size // SCS_RECORD_WORDS if rec is not None else 0) \
+            if nb_constraints is None else nb_constraints
+        h.ncoeffs = (co.size // FR_BYTES if co is not None else 0) if ncoeffs is None else ncoeffs
+        self.nb_constraints = h.nb_constraints
+        if rec is not None and rec.size:
+            h.records = rec.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+        if co is not None and co.size:
+            h.coeffs = co.ctypes.data
+        self.nb_bsb = h.nb_bsb = len(commitment_index)
+        if self.nb_bsb:
+            rows = [np.ascontiguousarray(c, dtype=np.uint32) for c in committed]
+            p32 = ctypes.POINTER(ctypes.c_uint32)
+            # an empty gate still gets a pointer: only its length says it is empty
+            lens = (ctypes.c_size_t * self.nb_bsb)(*[a.size for a in rows])
+            rows = [a if a.size else np.zeros(1, np.uint32) for a in rows]
+            tab = (p32 * self.nb_bsb)(*[a.ctypes.data_as(p32) for a in rows])
+            idx = (ctypes.c_size_t * self.nb_bsb)(*commitment_index)
+            h.committed, h.committed_len, h.commitment_index = tab, lens, idx
+        out = ctypes.c_void_p()
+        _check(load_library().gm_plonk_scs_upload(ctx.handle, curve_id(curve), ctypes.byref(h), ctypes.byref(out)))
+        self.handle = out
+
+    def wires(self) -> "PlonkWires":
+        """The wire tables inside the circuit (gm_plonk_scs_wires), for every call
+        that takes a PlonkWires.  Borrowed: freed with the circuit, and free() on
+        them is refused."""
+        h = ctypes.c_void_p()
+        _check(load_library().gm_plonk_scs_wires(self.handle, ctypes.byref(h)))
+        w = PlonkWires.__new__(PlonkWires)
+        w.ctx, w.n, w.nb_wires, w.handle = self.ctx, self.n, self.nb_wires, h
+        return w
+
+    def selector(self, which: int, out: DeviceBuffer | None = None) -> DeviceBuffer:
+        """gm_plonk_scs_selector: column `which` (SCS_QL .. SCS_QK, SCS_QCP0 + j) as n
+        elements on the device."""
+        own = out is None
+        if own:
+            out = self.ctx.malloc(FR_BYTES * self.n)
+        try:
+            _check(load_library().gm_plonk_scs_selector(self.ctx.handle, self.handle, which, out.ptr))
+        except GmError:
+            if own:
+                out.free()
+            raise
+        return out
+
+    def check(self, witness) -> tuple[int, int | None]:
+        """gm_plonk_scs_check: (number of unsatisfied constraints, the smallest such
+        constraint index or None)."""
+        w = _buf(witness) if witness is not None else None
+        cnt, first = ctypes.c_size_t(), ctypes.c_size_t(2**64 - 1)
+        _check(load_library().gm_plonk_scs_check(self.ctx.handle, self.handle, _p(w) if w is not None else None,
+                                                 ctypes.byref(cnt), ctypes.byref(first)))
+        return cnt.value, (None if first.value == 2**64 - 1 else first.value)
+
+    def resident_bytes(self) -> int:
+        a = ctypes.c_size_t()
+        _check(load_library().gm_plonk_scs_bytes(self.handle, ctypes.byref(a)))
+        return a.value
+
+    def free(self):
+        if self.handle:
+            _check(load_library().gm_plonk_scs_free(self.ctx.handle, self.handle))
             self.handle = None
 
 

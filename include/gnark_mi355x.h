@@ -641,6 +641,88 @@ int gm_plonk_sigma_wires(gm_ctx* ctx, int curve, const gm_plonk_wires* w,
 int gm_plonk_pk_setup_wires(gm_ctx* ctx, int curve, const gm_plonk_setup_host* in, const gm_plonk_wires* w,
                             unsigned flags, gm_plonk_pk** out, void* vk_digests, void* srs_lagrange_out);
 
+/* ---- PLONK circuit on the device (gnark NewTrace, backend/plonk/bls12-377/
+ *      setup.go:153-213; the PLONK twin of gm_r1cs_upload and gm_g16_pk_setup) ---------
+ * One resident object per compiled circuit, made from what gnark holds compactly:
+ * its []SparseR1C records as they lie in memory (constraint/r1cs_sparse.go:143-147,
+ * nine u32 = 36 bytes per constraint: XA XB XC QL QR QO QM QC Commitment), the
+ * CoeffTable (Montgomery fr.Elements, ids 0 and 1 being zero and one) and the
+ * PlonkCommitments (Committed and CommitmentIndex, both constraint indices).  The
+ * records go up once and a kernel splits them into the wire tables of
+ * evaluateLROSmallDomain (rows (i, 0, 0) for i < nb_public, the constraints from
+ * row nb_public on, (0, 0, 0) padding up to n), five columns of coefficient ids,
+ * one byte of Commitment per constraint, the coefficient table and the committed
+ * rows.  gm_plonk_scs_bytes reports the allocation.  No host pointer is kept.  The
+ * object is freed before its context; gm_destroy releases what a context still
+ * owns.  Curve ids 0 and 1.
+ *
+ * Everything is checked on the host before the first device call and
+ * gm_last_error names the first offender and its record.  GM_ERR_INVALID: a NULL
+ * argument; n not a power of two, n < 8, n > 2^30 or n < nb_public +
+ * nb_constraints; nb_wires = 0, nb_wires < nb_public or nb_wires > 2^32 - 1; a
+ * wire id >= nb_wires; a coefficient id >= ncoeffs; Commitment > 2; ncoeffs < 2;
+ * nb_bsb > 1024; a committed index or commitment index >= nb_constraints
+ * (duplicate committed indices are allowed); gm_plonk_scs_free on another context
+ * than the upload's.
+ *
+ * gm_plonk_scs_wires hands out the wire tables inside the object: every call
+ * that takes a gm_plonk_wires accepts them (gm_plonk_gather_lro,
+ * gm_plonk_session_round1_witness, gm_plonk_wires_permutation,
+ * gm_plonk_sigma_wires, gm_plonk_pk_setup_wires), gm_plonk_wires_free refuses them
+ * with GM_ERR_INVALID, and they are freed with the circuit.
+ *
+ * gm_plonk_scs_selector writes one of NewTrace's columns (n Fr, Lagrange regular)
+ * to out_dev: for GM_SCS_QL .. GM_SCS_QK, -1 (QL) or 0 on the rows of the public
+ * inputs, coeffs[id] on the constraint rows, 0 on the padding (QK incomplete, as
+ * gm_plonk_pk_host takes it); for GM_SCS_QCP0 + j, 1 on the rows nb_public +
+ * Committed[j][i] and 0 elsewhere.  One launch per column.  GM_ERR_INVALID: a
+ * NULL argument, which >= GM_SCS_QCP0 + nb_bsb, a circuit of another context,
+ * out_dev not 16-byte aligned or overlapping the object.
+ *
+ * gm_plonk_pk_setup_scs is gm_plonk_pk_setup_wires with nothing dense from the
+ * host: the curve, n, nb_public, nb_bsb and the commitment rows (nb_public +
+ * CommitmentIndex[j]) come from the object, the permutation from its tables, and
+ * every selector is generated on the device where the _wires call copies a host
+ * vector.  The key, vk_digests (S1 S2 S3 Ql Qr Qm Qo Qk Qcp_j), srs_lagrange_out,
+ * the flags and the refusals are those of the _wires call given the same
+ * selectors.  The key does not refer to the circuit afterwards.  With it Setup
+ * needs the constraint system and the canonical SRS, and a session's
+ * gm_plonk_session_round1_witness needs the witness.
+ *
+ * gm_plonk_scs_check evaluates ql l + qr r + qm l r + qo o + qk on every
+ * constraint whose Commitment is NOT (gnark's solver skips the others,
+ * constraint/blueprint_scs.go:56-60) for a witness of nb_wires Fr on the host:
+ * nb_unsatisfied receives the number of constraints where it is not zero,
+ * first_unsatisfied the smallest such constraint index (untouched if there is
+ * none).  Public placeholder rows and padding rows are not evaluated.  Returns
+ * with the stream drained.  GM_ERR_INVALID: a NULL argument, a circuit of another
+ * context. */
+typedef struct gm_plonk_scs gm_plonk_scs;
+typedef struct {
+  size_t n;                 /* domain0 size: power of two, >= 8, >= nb_public + nb_constraints */
+  size_t nb_public, nb_constraints, nb_wires;
+  const uint32_t* records;  /* host, nb_constraints records of 9 u32 */
+  const void* coeffs;       /* host, ncoeffs fr.Element, Montgomery: the CoeffTable */
+  size_t ncoeffs;
+  size_t nb_bsb;
+  const uint32_t* const* committed;   /* nb_bsb host arrays: PlonkCommitment.Committed */
+  const size_t* committed_len;
+  const size_t* commitment_index;     /* nb_bsb: PlonkCommitment.CommitmentIndex */
+} gm_plonk_scs_host;
+int gm_plonk_scs_upload(gm_ctx* ctx, int curve, const gm_plonk_scs_host* in, gm_plonk_scs** out);
+int gm_plonk_scs_bytes(const gm_plonk_scs* scs, size_t* resident_bytes);
+int gm_plonk_scs_free(gm_ctx* ctx, gm_plonk_scs* scs);
+int gm_plonk_scs_wires(const gm_plonk_scs* scs, const gm_plonk_wires** out /* borrowed */);
+enum { GM_SCS_QL, GM_SCS_QR, GM_SCS_QM, GM_SCS_QO, GM_SCS_QK, GM_SCS_QCP0 /* + j */ };
+int gm_plonk_scs_selector(gm_ctx* ctx, const gm_plonk_scs* scs, unsigned which,
+                          void* out_dev /* device, n Fr, Lagrange regular */);
+int gm_plonk_pk_setup_scs(gm_ctx* ctx, const gm_plonk_scs* scs, const void* srs_canonical,
+                          size_t srs_canonical_len, unsigned flags, gm_plonk_pk** out,
+                          void* vk_digests /* host, 8 + nb_bsb G1Affine */,
+                          void* srs_lagrange_out /* host, n G1Affine, or NULL */);
+int gm_plonk_scs_check(gm_ctx* ctx, const gm_plonk_scs* scs, const void* witness_host /* nb_wires Fr */,
+                       size_t* nb_unsatisfied, size_t* first_unsatisfied /* constraint index */);
+
 /* ---- NTT (iciclegnark GenerateTwiddleFactors icicle.go:68,73;
  *      INttOnDevice :489,502; NttOnDevice :490; PolyOps :500;
  *      ReverseScalars :510; CPU twin fft.Domain.FFT/FFTInverse
