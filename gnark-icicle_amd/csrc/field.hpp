@@ -635,6 +635,22 @@ GM_DEV Fe<P> fe_inv(const Fe<P>& a) {
   return r;
 }
 
+// base^e by square-and-multiply from the low bit, internal form in and out.
+template <class P>
+GM_DEV Fe<P> fe_pow(const Fe<P>& base, uint64_t e) {
+  Fe<P> r = fe_one<P>();
+  Fe<P> b = base;
+  while (e) {
+    if (e & 1) r = fe_mul(r, b);
+    e >>= 1;
+    if (e) b = fe_sqr(b);
+  }
+  return r;
+}
+
+// the low `bits` bits of x in reverse order (bits <= 32; 0 at bits == 0)
+GM_DEV uint32_t brev_bits(uint32_t x, int bits) { return bits ? (__brev(x) >> (32 - bits)) : 0; }
+
 // ---------------------------------------------------------------------------
 // Quadratic extension Fp2 = Fp[u]/(u^2 - BETA).  BN254: BETA = -1;
 // BLS12-377: BETA = -5 (gnark-crypto E2 layout: {A0, A1}).

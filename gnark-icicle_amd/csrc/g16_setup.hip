@@ -45,7 +45,7 @@
 #include "groth16.hpp"
 #include "ntt.hpp"
 #include "runtime.hpp"
-#include "sort_util.hpp"
+#include "scan.hpp"
 
 namespace gm {
 
@@ -316,56 +316,8 @@ namespace {
 constexpr uint32_t COL_SHORT = 32;
 constexpr uint32_t COL_CUT_DEFAULT = 1u << 14;
 constexpr unsigned COL_TPB = 256;
-constexpr uint32_t SCAN_BLK = 4096;
-constexpr size_t SCAN_MAX = (size_t)8192 * SCAN_BLK;
-
-// ---- device-wide exclusive scan of n u32, out[n] = total (n <= SCAN_MAX) ------
-__global__ void __launch_bounds__(1024) k_gs_scan_local(const uint32_t* __restrict__ in, uint32_t n,
-                                                        uint32_t* __restrict__ out, uint32_t* __restrict__ bsum) {
-  __shared__ uint32_t a[SCAN_BLK], wsum[17];
-  const uint32_t base = blockIdx.x * SCAN_BLK, len = min(SCAN_BLK, n - base);
-  for (uint32_t q = threadIdx.x; q < len; q += S_THREADS) a[q] = in[base + q];
-  const uint32_t tot = block_excl_scan(a, len, wsum);
-  for (uint32_t q = threadIdx.x; q < len; q += S_THREADS) out[base + q] = a[q];
-  if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-__global__ void __launch_bounds__(1024) k_gs_scan_tops(uint32_t* __restrict__ bsum, uint32_t nblk) {
-  __shared__ uint32_t a[8192], wsum[17];
-  for (uint32_t q = threadIdx.x; q < nblk; q += S_THREADS) a[q] = bsum[q];
-  const uint32_t tot = block_excl_scan(a, nblk, wsum);
-  for (uint32_t q = threadIdx.x; q < nblk; q += S_THREADS) bsum[q] = a[q];
-  if (threadIdx.x == 0) bsum[nblk] = tot;
-}
-__global__ void __launch_bounds__(256) k_gs_scan_add(uint32_t* __restrict__ out, uint32_t n,
-                                                     const uint32_t* __restrict__ bsum, uint32_t nblk) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] += bsum[i / SCAN_BLK];
-  if (i == 0) out[n] = bsum[nblk];
-}
-// in: n counts; out: n + 1 offsets; bsum: blocks_for(n, SCAN_BLK) + 1 words
-int device_scan(gm_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out, uint32_t* bsum) {
-  if (n == 0) {
-    GM_HIP(hipMemsetAsync(out, 0, sizeof(uint32_t), ctx->stream));
-    return GM_OK;
-  }
-  const uint32_t nblk = blocks_for(n, SCAN_BLK);
-  hipLaunchKernelGGL(k_gs_scan_local, dim3(nblk), dim3(S_THREADS), 0, ctx->stream, in, (uint32_t)n, out, bsum);
-  hipLaunchKernelGGL(k_gs_scan_tops, dim3(1), dim3(S_THREADS), 0, ctx->stream, bsum, nblk);
-  hipLaunchKernelGGL(k_gs_scan_add, dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream, out, (uint32_t)n,
-                     (const uint32_t*)bsum, nblk);
-  GM_HIP(hipGetLastError());
-  return GM_OK;
-}
-
-template <class Fr>
-GM_DEV Fe<Fr> fe_pow_internal(Fe<Fr> b, size_t e) {
-  Fe<Fr> r = fe_one<Fr>();
-  for (; e; e >>= 1) {
-    if (e & 1) r = fe_mul(r, b);
-    b = fe_sqr(b);
-  }
-  return r;
-}
+// the documented limit of gm_g16_setup: wires, constraints
+constexpr size_t SETUP_MAX = (size_t)1 << 25;
 
 // ---- Lagrange values ---------------------------------------------------------
 // lane j: wj[j] = w^j (gnark form), den[j] = tau - w^j (internal form), and the
@@ -378,7 +330,7 @@ __global__ void __launch_bounds__(256)
   const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
   Fe<Fr> d = fe_one<Fr>();
   if (j < nc) {
-    const Fe<Fr> w = fe_pow_internal(fe_to_internal(fe_unpack<Fr>(omega)), j);
+    const Fe<Fr> w = fe_pow(fe_to_internal(fe_unpack<Fr>(omega)), j);
     d = fe_sub(fe_to_internal(fe_unpack<Fr>(tau)), w);
     fe_store_g<Fr>(wj, j, fe_to_gnark(w));
     den[j] = d;
@@ -535,8 +487,8 @@ __global__ void __launch_bounds__(256)
     k_setup_z(size_t n, uint32_t logn, FeG<Fr> tau, FeG<Fr> scale, uint32_t* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i + 1 >= n) return;
-  const size_t src = logn ? (size_t)(__brevll((unsigned long long)i) >> (64 - logn)) : 0;
-  const Fe<Fr> p = fe_pow_internal(fe_to_internal(fe_unpack<Fr>(tau)), src);
+  const size_t src = brev_bits((uint32_t)i, (int)logn);  // n <= SETUP_MAX
+  const Fe<Fr> p = fe_pow(fe_to_internal(fe_unpack<Fr>(tau)), src);
   fe_store_g<Fr>(out, i, fe_mul(fe_unpack<Fr>(scale), p));
 }
 
@@ -583,7 +535,7 @@ int setup_judge(const char* entry, const gm_r1cs* r, const gm_g16_setup_in* in, 
   if (h.delta.is_zero()) return refuse_setup(entry, "delta is zero");
   if (h.gamma.is_zero()) return refuse_setup(entry, "gamma is zero");
   while (h.n < r->nc) h.n <<= 1, h.logn++;
-  if (r->nb_wires + 1 > SCAN_MAX || h.n > SCAN_MAX)
+  if (r->nb_wires + 1 > SETUP_MAX || h.n > SETUP_MAX)
     return refuse_setup(entry, "more than 2^25 wires or constraints");
   h.omega = HF::one();
   if (h.logn)
@@ -627,7 +579,7 @@ int column_sums(gm_ctx* ctx, Arena& arena, const gm_r1cs* r, int m, const uint32
   int rc;
   DevBuf counts, colptr, cursor, bsum, trow, tcid, llist, lcount;
   if ((rc = counts.alloc(arena, 4 * (nw + 1))) || (rc = colptr.alloc(arena, 4 * (nw + 1))) ||
-      (rc = cursor.alloc(arena, 4 * (nw + 1))) || (rc = bsum.alloc(arena, 4 * (blocks_for(nw + 1, SCAN_BLK) + 1))) ||
+      (rc = cursor.alloc(arena, 4 * (nw + 1))) || (rc = bsum.alloc(arena, 4 * scan_ws_words(nw))) ||
       (rc = trow.alloc(arena, 4 * (nnz + 1))) || (rc = tcid.alloc(arena, 4 * (nnz + 1))) ||
       (rc = llist.alloc(arena, 12 * (size_t)long_cap)) || (rc = lcount.alloc(arena, 4)))
     return rc;
@@ -638,7 +590,7 @@ int column_sums(gm_ctx* ctx, Arena& arena, const gm_r1cs* r, int m, const uint32
     if (nnz)
       hipLaunchKernelGGL(k_col_hist, dim3(blocks_for(nnz, 256)), dim3(256), 0, ctx->stream, r->vid[m], nnz,
                          counts.as<uint32_t>());
-    if ((rc = device_scan(ctx, counts.as<uint32_t>(), nw, colptr.as<uint32_t>(), bsum.as<uint32_t>()))) return rc;
+    if ((rc = device_excl_scan(ctx, counts.as<uint32_t>(), nw, colptr.as<uint32_t>(), bsum.as<uint32_t>()))) return rc;
     GM_HIP(hipMemcpyAsync(cursor.p, colptr.p, 4 * (nw + 1), hipMemcpyDeviceToDevice, ctx->stream));
     if (r->nc)
       hipLaunchKernelGGL(k_col_scatter, dim3(blocks_for(r->nc, 256)), dim3(256), 0, ctx->stream, r->rowptr[m], r->nc,
@@ -734,14 +686,14 @@ int setup_scalars(gm_ctx* ctx, Arena& arena, const gm_r1cs* r, const SetupHost<C
     ProfScope ps(ctx, "g16_setup_compact");
     DevBuf keep, pos, bsum;
     if ((rc = keep.alloc(arena, 4 * (nw + 1))) || (rc = pos.alloc(arena, 4 * (nw + 1))) ||
-        (rc = bsum.alloc(arena, 4 * (blocks_for(nw + 1, SCAN_BLK) + 1))))
+        (rc = bsum.alloc(arena, 4 * scan_ws_words(nw))))
       return rc;
     for (int x = 0; x < 2; x++) {
       uint32_t total = 0;
       if (nw) {
         hipLaunchKernelGGL(k_zero_flags, dim3(blocks_for(nw, 256)), dim3(256), 0, ctx->stream,
                            s.sum[x].as<uint4>(), nw, s.inf[x].as<uint8_t>(), keep.as<uint32_t>());
-        if ((rc = device_scan(ctx, keep.as<uint32_t>(), nw, pos.as<uint32_t>(), bsum.as<uint32_t>()))) return rc;
+        if ((rc = device_excl_scan(ctx, keep.as<uint32_t>(), nw, pos.as<uint32_t>(), bsum.as<uint32_t>()))) return rc;
         if (!counts_only)
           hipLaunchKernelGGL(k_compact, dim3(blocks_for(nw, 256)), dim3(256), 0, ctx->stream, s.sum[x].as<uint4>(),
                              nw, (const uint32_t*)keep.as<uint32_t>(), (const uint32_t*)pos.as<uint32_t>(),

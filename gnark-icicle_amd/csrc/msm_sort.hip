@@ -28,6 +28,7 @@
 // values (+ 4 B of keys) written (staged bins).
 #include "msm.hpp"
 #include "runtime.hpp"
+#include "scan.hpp"
 #include "sort_util.hpp"
 
 namespace gm {
@@ -296,32 +297,6 @@ static __global__ void __launch_bounds__(1024) k_msm_sm_scatter(const E* __restr
   }
 }
 
-// Device-wide exclusive scan of n u32 (out[n] = total): block scans of
-// SCAN_BLK elements, one block over the block totals, then the fix-up.
-constexpr uint32_t SCAN_BLK = 4096;
-static __global__ void __launch_bounds__(1024) k_scan_local(const uint32_t* __restrict__ in, uint32_t n,
-                                                            uint32_t* __restrict__ out, uint32_t* __restrict__ bsum) {
-  __shared__ uint32_t a[SCAN_BLK], wsum[17];
-  const uint32_t base = blockIdx.x * SCAN_BLK, len = min(SCAN_BLK, n - base);
-  for (uint32_t q = threadIdx.x; q < len; q += S_THREADS) a[q] = in[base + q];
-  const uint32_t tot = block_excl_scan(a, len, wsum);
-  for (uint32_t q = threadIdx.x; q < len; q += S_THREADS) out[base + q] = a[q];
-  if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-static __global__ void __launch_bounds__(1024) k_scan_tops(uint32_t* __restrict__ bsum, uint32_t nblk) {
-  __shared__ uint32_t a[8192], wsum[17];
-  for (uint32_t q = threadIdx.x; q < nblk; q += S_THREADS) a[q] = bsum[q];
-  const uint32_t tot = block_excl_scan(a, nblk, wsum);
-  for (uint32_t q = threadIdx.x; q < nblk; q += S_THREADS) bsum[q] = a[q];
-  if (threadIdx.x == 0) bsum[nblk] = tot;
-}
-static __global__ void __launch_bounds__(1024) k_scan_add(uint32_t* __restrict__ out, uint32_t n,
-                                                          const uint32_t* __restrict__ bsum, uint32_t nblk) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] += bsum[i / SCAN_BLK];
-  if (i == 0) out[n] = bsum[nblk];
-}
-
 // LDS layout: hist[2^F] | staged values[S2_STAGE] | (KEYS) staged keys[S2_STAGE].
 // kb = F + G: the key bits a compact entry carries (SortEnt); an entry's bucket
 // is its coarse bin's first bucket + its low F bits.  KEYS false: keys_out is
@@ -518,27 +493,19 @@ static int sort_passes(gm_ctx* ctx, Arena& arena, const SortGeom& g, size_t n, u
   const uint32_t *cbase = sbase.as<uint32_t>(), *pbase = spbase.as<uint32_t>();
   if (g.G) {
     DevBuf ccount, cb, ccur, cparts, pb, bsum, tmp2;
-    const uint32_t nblk = (g.NC + SCAN_BLK - 1) / SCAN_BLK;
     if ((rc = ccount.alloc(arena, 4 * (size_t)g.NC)) || (rc = cb.alloc(arena, 4 * ((size_t)g.NC + 1))) ||
         (rc = ccur.alloc(arena, 4 * (size_t)g.NC)) || (rc = cparts.alloc(arena, 4 * (size_t)g.NC)) ||
-        (rc = pb.alloc(arena, 4 * ((size_t)g.NC + 1))) || (rc = bsum.alloc(arena, 4 * ((size_t)nblk + 1))) ||
+        (rc = pb.alloc(arena, 4 * ((size_t)g.NC + 1))) || (rc = bsum.alloc(arena, 4 * scan_ws_words(g.NC))) ||
         (rc = tmp2.alloc(arena, sizeof(E) * g.M)))
       return rc;
-    if (nblk > 8192) {
-      set_error("msm sort: too many coarse bins");
-      return GM_ERR_INVALID;
-    }
     const size_t mparts = (size_t)g.NS + g.M / SM_PART + 1;
     GM_HIP(hipMemsetAsync(ccount.p, 0, 4 * (size_t)g.NC, st));
     hipLaunchKernelGGL(k_msm_sm_count<E>, dim3((unsigned)mparts), dim3(S_THREADS), 0, st, tmp.as<E>(),
                        sbase.as<uint32_t>(), spbase.as<uint32_t>(), g.NS, g.F, g.G, ccount.as<uint32_t>());
     hipLaunchKernelGGL(k_msm_sm_scan, dim3(g.NS), dim3(S_THREADS), 0, st, ccount.as<uint32_t>(), sbase.as<uint32_t>(),
                        g.G, g.NC, cb.as<uint32_t>(), ccur.as<uint32_t>(), cparts.as<uint32_t>());
-    hipLaunchKernelGGL(k_scan_local, dim3(nblk), dim3(S_THREADS), 0, st, cparts.as<uint32_t>(), g.NC,
-                       pb.as<uint32_t>(), bsum.as<uint32_t>());
-    hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(S_THREADS), 0, st, bsum.as<uint32_t>(), nblk);
-    hipLaunchKernelGGL(k_scan_add, dim3(blocks_for(g.NC, 256)), dim3(256), 0, st, pb.as<uint32_t>(), g.NC,
-                       bsum.as<uint32_t>(), nblk);
+    // NC <= NS << G <= 2^23 coarse bins (msm_sort_digits checks NS <= 8192, G <= 10)
+    if ((rc = device_excl_scan(ctx, cparts.as<uint32_t>(), g.NC, pb.as<uint32_t>(), bsum.as<uint32_t>()))) return rc;
     hipLaunchKernelGGL(k_msm_sm_scatter<E>, dim3((unsigned)mparts), dim3(S_THREADS), 0, st, tmp.as<E>(),
                        sbase.as<uint32_t>(), spbase.as<uint32_t>(), g.NS, g.F, g.G, ccur.as<uint32_t>(),
                        tmp2.as<E>());

@@ -42,8 +42,6 @@ GM_DEV Fe<P> ld_tab(const Fe<P>* __restrict__ t, size_t i) {
   return t[i];
 }
 
-GM_DEV uint32_t brev_bits(uint32_t x, int bits) { return bits ? (__brev(x) >> (32 - bits)) : 0; }
-
 // One pass over index bits [lo, lo+t).  sub: w_T^x for x < T/2 (T = 2^t);
 // tw: inter-pass twiddles (null if lo == 0).  Fused element-wise factors, all
 // indexed by the element's global address:
@@ -692,18 +690,6 @@ __global__ void __launch_bounds__(NTT_TPB) __attribute__((amdgpu_waves_per_eu(DI
 // ---------------------------------------------------------------------------
 // table generation
 // ---------------------------------------------------------------------------
-template <class P>
-GM_DEV Fe<P> fe_pow_u32(const Fe<P>& base, uint32_t e) {
-  Fe<P> r = fe_one<P>();
-  Fe<P> b = base;
-  while (e) {
-    if (e & 1) r = fe_mul(r, b);
-    e >>= 1;
-    if (e) b = fe_sqr(b);
-  }
-  return r;
-}
-
 // tw[j*2^lo + L] = w^(L * bitrev_t(j)), w = w_{2^(lo+t)} (canonical exponent < 2^(lo+t));
 // w arrives in gnark form, tables are written in internal form.
 template <class P>
@@ -716,7 +702,7 @@ __global__ void k_gen_pass_tw(Fe<P>* __restrict__ tw, int lo, int t, FeG<P> wg, 
   const uint32_t j = (uint32_t)(i >> lo), L = (uint32_t)(i & (((size_t)1 << lo) - 1));
   const uint64_t e = (uint64_t)L * brev_bits(j, t);
   // e < 2^(lo+t) <= 2^32 for supported sizes
-  tw[i] = fe_mul(fe_pow_u32(w, (uint32_t)e), mult);
+  tw[i] = fe_mul(fe_pow(w, (uint32_t)e), mult);
 }
 
 // out[x] = base^x * mult, x < count (gnark-form inputs, internal-form table)
@@ -726,7 +712,7 @@ __global__ void k_gen_powers(Fe<P>* __restrict__ out, size_t count, FeG<P> base_
   if (i >= count) return;
   const Fe<P> base = fe_to_internal(fe_unpack<P>(base_g));
   const Fe<P> mult = fe_to_internal(fe_unpack<P>(mult_g));
-  out[i] = fe_mul(fe_pow_u32(base, (uint32_t)i), mult);
+  out[i] = fe_mul(fe_pow(base, (uint32_t)i), mult);
 }
 
 // out[i] = mult * base^e, e = i or bitrev_logn(i) (full-size coset tables;
@@ -738,7 +724,7 @@ __global__ void k_gen_coset(Fe<P>* __restrict__ out, size_t n, int logn, FeG<P> 
   const Fe<P> base = fe_to_internal(fe_unpack<P>(base_g));
   const Fe<P> mult = fe_to_internal(fe_unpack<P>(mult_g));
   const uint32_t e = BREV ? brev_bits((uint32_t)i, logn) : (uint32_t)i;
-  out[i] = fe_mul(fe_pow_u32(base, e), mult);
+  out[i] = fe_mul(fe_pow(base, e), mult);
 }
 
 template <class P>

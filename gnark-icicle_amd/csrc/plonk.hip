@@ -65,8 +65,6 @@ struct QuotCoset {
   FeG<P> k_lag;                // internal: alpha^2 2^(29 N - 256) / Z_H(c_i)
 };
 
-GM_DEV uint32_t pq_brev(uint32_t x, int bits) { return __brev(x) >> (32 - bits); }
-
 // ev: the (PQ_FIXED + 2 nb) coset evaluations, slot k at element k n; out: the
 // coset's block of the 4n vector.  Lane p reads element p of every slot (32 B,
 // consecutive lanes consecutive) and one element of the Z slot elsewhere.
@@ -105,7 +103,7 @@ __global__ void __launch_bounds__(PLONK_TPB) k_plonk_constraint(const void* __re
   };
   auto U = [](const FeG<P>& g) { return fe_unpack<P>(g); };
   // Z(w0 x): evaluation index brev(p) + 1 mod n
-  const size_t pn = pq_brev((pq_brev((uint32_t)p, logn) + 1) & (uint32_t)(n - 1), logn);
+  const size_t pn = brev_bits((brev_bits((uint32_t)p, logn) + 1) & (uint32_t)(n - 1), logn);
   const Fe<P> x = fe_mul(wbrev[p], U(q.c));  // internal
   const Fe<P> x2 = fe_sqr(x);
   // blinded wires, internal form: W + Z_H (b0 + b1 x)

@@ -84,8 +84,6 @@ struct PermK {
   FeG<P> one_g;    // gnark: Z[0]
 };
 
-GM_DEV uint32_t perm_brev(uint32_t x, int bits) { return __brev(x) >> (32 - bits); }
-
 // beta g^k w^i for the rows row0 + r TPB of one lane, gnark form
 template <class P>
 struct PermX {
@@ -100,11 +98,11 @@ GM_DEV PermX<P> perm_x_init(const PermK<P>& k, const Fe<P>* __restrict__ wbrev, 
   x.step = fe_one<P>();
   if (row0 < n) {
     const Fe<P> g = fe_unpack<P>(k.g_i);
-    x.bx[0] = fe_mul(wbrev[perm_brev((uint32_t)row0, logn)], fe_unpack<P>(k.beta_g));
+    x.bx[0] = fe_mul(wbrev[brev_bits((uint32_t)row0, logn)], fe_unpack<P>(k.beta_g));
     x.bx[1] = fe_mul(x.bx[0], g);
     x.bx[2] = fe_mul(x.bx[1], g);
   }
-  if ((size_t)PERM_TPB < n) x.step = wbrev[perm_brev((uint32_t)PERM_TPB, logn)];
+  if ((size_t)PERM_TPB < n) x.step = wbrev[brev_bits((uint32_t)PERM_TPB, logn)];
   return x;
 }
 

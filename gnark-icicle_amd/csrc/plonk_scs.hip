@@ -37,17 +37,10 @@ void plonk_scs_release(gm_plonk_scs* s) {
 
 namespace {
 
-constexpr unsigned SCS_TPB = 256;
-// grid-stride above this many blocks: 8 blocks of 256 lanes on each of 256 CUs
-constexpr unsigned SCS_MAX_BLOCKS = 2048;
+constexpr unsigned SCS_TPB = 256;  // the block of grid_for (runtime.hpp)
 constexpr unsigned REC_WORDS = 9;  // XA XB XC QL QR QO QM QC Commitment
 // SparseR1C.Commitment (constraint/r1cs_sparse.go): NOT, COMMITTED, COMMITMENT
 constexpr uint32_t COMMITMENT_NOT = 0, COMMITMENT_MAX = 2;
-
-unsigned grid_for(size_t lanes) {
-  const size_t b = (lanes + SCS_TPB - 1) / SCS_TPB;
-  return (unsigned)std::min<size_t>(std::max<size_t>(b, 1), SCS_MAX_BLOCKS);
-}
 
 // A tile of 256 records goes through LDS: the block reads its 2304 words in
 // order (coalesced u32), then lane t takes record t and writes one entry of each

@@ -92,12 +92,7 @@ __global__ void __launch_bounds__(256) k_powers(uint32_t* __restrict__ out, size
   static_assert(Fr::NG == 8 && Fr::BITS <= 254, "scalar fields of 8 u32 words, 3 k < 2^256");
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
-  Fe<Fr> b = fe_to_internal(fe_unpack<Fr>(base_gnark));
-  Fe<Fr> r = fe_one<Fr>();
-  for (size_t e = i; e; e >>= 1) {
-    if (e & 1) r = fe_mul(r, b);
-    b = fe_sqr(b);
-  }
+  const Fe<Fr> r = fe_pow(fe_to_internal(fe_unpack<Fr>(base_gnark)), i);
   if constexpr (NAF) {
     const Naf d = naf_of(fe_pack(fe_from_mont(r)).w);
     uint4* const dst = reinterpret_cast<uint4*>(out + i * NAF_WORDS);
@@ -188,7 +183,7 @@ __global__ void __launch_bounds__(ECFFT_TPB) k_ecfft_store(const XYZZ<F>* __rest
                                                            uint32_t* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * ECFFT_TPB + threadIdx.x;
   if (i >= ((size_t)1 << logn)) return;
-  const size_t src = (size_t)(__brevll((unsigned long long)i) >> (64 - logn));
+  const size_t src = brev_bits((uint32_t)i, (int)logn);  // logn <= 30
   const XYZZ<F> acc = xyzz_mul_naf<true>(pts[src], ninv);
   Affine<F> r;
   if (xyzz_is_inf(acc)) {

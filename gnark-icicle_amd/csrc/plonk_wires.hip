@@ -36,14 +36,7 @@ void plonk_wires_release(gm_plonk_wires* w) {
 
 namespace {
 
-constexpr unsigned WIRES_TPB = 256;
-// grid-stride above this many blocks: 8 blocks of 256 lanes on each of 256 CUs
-constexpr unsigned WIRES_MAX_BLOCKS = 2048;
-
-unsigned grid_for(size_t lanes) {
-  const size_t b = (lanes + WIRES_TPB - 1) / WIRES_TPB;
-  return (unsigned)std::min<size_t>(std::max<size_t>(b, 1), WIRES_MAX_BLOCKS);
-}
+constexpr unsigned WIRES_TPB = 256;  // the block of grid_for (runtime.hpp)
 
 // lane t: half t & 1 of row t >> 1 of all three outputs
 __global__ void __launch_bounds__(WIRES_TPB)

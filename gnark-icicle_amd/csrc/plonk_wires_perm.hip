@@ -8,7 +8,7 @@
 //     wire's run.  Least-significant-digit radix sort, 8-bit digits, as many
 //     passes as nb_wires - 1 has bytes (none for nb_wires = 1).  A pass is
 //       k_wp_hist     per tile of 2048 entries, the count of every digit;
-//       the scan      exclusive, device-wide, over (digit, tile);
+//       the scan      exclusive, device-wide (scan.hpp), over (digit, tile);
 //       k_wp_scatter  every entry to scan[digit][tile] + its rank among the
 //                     tile's entries of that digit.
 //     The rank is what makes the sort stable.  A tile is dealt out so that (wave,
@@ -40,6 +40,7 @@
 #include <string>
 
 #include "plonk_wires_perm.hpp"
+#include "scan.hpp"
 #include "sort_util.hpp"
 
 namespace gm {
@@ -53,14 +54,6 @@ constexpr unsigned WP_WAVE_SPAN = 64 * WP_ROUNDS;      // consecutive entries of
 constexpr unsigned WP_DIGITS = 256;
 static_assert(WP_DIGITS == WP_TPB, "thread d owns digit d");
 constexpr unsigned WP_LINK_TPB = 1024;                 // the link's tile: one entry per thread
-constexpr uint32_t WP_SCAN_BLK = 4096;
-// grid-stride above this many blocks of 256 lanes (as plonk_wires.hip)
-constexpr unsigned WP_MAX_BLOCKS = 2048;
-
-unsigned wp_grid(size_t lanes) {
-  const size_t b = (lanes + 255) / 256;
-  return (unsigned)std::min<size_t>(std::max<size_t>(b, 1), WP_MAX_BLOCKS);
-}
 
 // the valid lanes of the wave that hold the same 8-bit digit as this lane
 __device__ __forceinline__ uint64_t wp_match(uint32_t d, bool valid) {
@@ -72,47 +65,6 @@ __device__ __forceinline__ uint64_t wp_match(uint32_t d, bool valid) {
     m &= bit ? bal : ~bal;
   }
   return m;
-}
-
-template <bool MAX>
-__device__ __forceinline__ uint32_t wp_op(uint32_t a, uint32_t b) {
-  return MAX ? max(a, b) : a + b;
-}
-template <bool MAX>
-__device__ __forceinline__ uint32_t wp_wave_incl(uint32_t v) {
-  const uint32_t lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t u = __shfl_up(v, d, 64);
-    if (lane >= (uint32_t)d) v = wp_op<MAX>(v, u);
-  }
-  return v;
-}
-// exclusive scan (sum, or max with identity 0) of one value per thread over a
-// 1024-thread block; *total receives the block's result.  ws: 17 words of LDS.
-// Synchronises on entry and exit.
-template <bool MAX>
-__device__ __forceinline__ uint32_t wp_block_excl(uint32_t v, uint32_t* ws, uint32_t* total) {
-  __syncthreads();
-  const uint32_t t = threadIdx.x, lane = t & 63;
-  const uint32_t inc = wp_wave_incl<MAX>(v);
-  uint32_t exc = __shfl_up(inc, 1, 64);
-  if (lane == 0) exc = 0;
-  if (lane == 63) ws[t >> 6] = inc;
-  __syncthreads();
-  if (t < 64) {
-    const uint32_t x = t < 16 ? ws[t] : 0u;
-    const uint32_t xi = wp_wave_incl<MAX>(x);
-    uint32_t xe = __shfl_up(xi, 1, 64);
-    if (t == 0) xe = 0;
-    if (t < 16) ws[t] = xe;
-    if (t == 15) ws[16] = xi;
-  }
-  __syncthreads();
-  const uint32_t r = wp_op<MAX>(ws[t >> 6], exc);
-  *total = ws[16];
-  __syncthreads();
-  return r;
 }
 
 // the key of sorted entry i as a pass reads it
@@ -231,42 +183,6 @@ __global__ void __launch_bounds__(WP_TPB)
   }
 }
 
-// ---- device-wide exclusive scan of len u32 in place ---------------------------
-// blocks of 4096: local scan, the block's total to bsum
-__global__ void __launch_bounds__(S_THREADS)
-    k_wp_scan_local(uint32_t* __restrict__ a, size_t len, uint32_t* __restrict__ bsum) {
-  __shared__ uint32_t s[WP_SCAN_BLK], wsum[17];
-  const size_t base = (size_t)blockIdx.x * WP_SCAN_BLK;
-  const uint32_t n = (uint32_t)min((size_t)WP_SCAN_BLK, len - base);
-  for (uint32_t q = threadIdx.x; q < n; q += S_THREADS) s[q] = a[base + q];
-  const uint32_t tot = block_excl_scan(s, n, wsum);
-  for (uint32_t q = threadIdx.x; q < n; q += S_THREADS) a[base + q] = s[q];
-  if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-// one block, any length: thread t scans the t-th slice of a in place (sum, or max
-// with identity 0)
-template <bool MAX>
-__global__ void __launch_bounds__(S_THREADS) k_wp_scan_one(uint32_t* __restrict__ a, uint32_t len) {
-  __shared__ uint32_t ws[17];
-  const uint32_t t = threadIdx.x;
-  const uint32_t per = (len + S_THREADS - 1) / S_THREADS;
-  const uint32_t lo = min(t * per, len), hi = min(lo + per, len);
-  uint32_t acc = 0;
-  for (uint32_t q = lo; q < hi; q++) acc = wp_op<MAX>(acc, a[q]);
-  uint32_t total;
-  uint32_t run = wp_block_excl<MAX>(acc, ws, &total);
-  for (uint32_t q = lo; q < hi; q++) {
-    const uint32_t x = a[q];
-    a[q] = run;
-    run = wp_op<MAX>(run, x);
-  }
-}
-__global__ void __launch_bounds__(256)
-    k_wp_scan_add(uint32_t* __restrict__ a, size_t len, const uint32_t* __restrict__ bsum) {
-  const size_t stride = (size_t)gridDim.x * 256;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < len; i += stride) a[i] += bsum[i / WP_SCAN_BLK];
-}
-
 // the sorted order of a single wire: the identity
 __global__ void __launch_bounds__(256) k_wp_iota(uint32_t* __restrict__ pos, uint32_t N) {
   const size_t stride = (size_t)gridDim.x * 256;
@@ -312,7 +228,7 @@ __global__ void __launch_bounds__(WP_LINK_TPB)
   const bool tail = valid && (i + 1 == N || sk[t + 2] != k);
   uint32_t total;
   const uint32_t v = head ? (uint32_t)i + 1 : 0u;
-  const uint32_t hd = max(wp_block_excl<true>(v, ws, &total), v);  // 1 + my run's head, 0: before the tile
+  const uint32_t hd = max(block_excl<true>(v, ws, &total), v);  // 1 + my run's head, 0: before the tile
   if (valid && !head) out[p] = (OUT)sp[t];
   if (tail) {
     if (hd)
@@ -356,7 +272,7 @@ int sort_pass(gm_ctx* ctx, int pass, const uint32_t* tab, const uint32_t* pos_in
               uint32_t tiles, uint32_t* hist, uint32_t* bsum, uint32_t* pos_out, uint32_t* key_out) {
   const uint32_t shift = 8u * (uint32_t)pass;
   const size_t cells = (size_t)WP_DIGITS * tiles;
-  const uint32_t nblk = (uint32_t)((cells + WP_SCAN_BLK - 1) / WP_SCAN_BLK);
+  int rc;
   {
     ProfScope ps(ctx, HIST_NAMES[pass]);
     auto k = pass == 0 ? k_wp_hist<true> : k_wp_hist<false>;
@@ -364,10 +280,7 @@ int sort_pass(gm_ctx* ctx, int pass, const uint32_t* tab, const uint32_t* pos_in
   }
   {
     ProfScope ps(ctx, SCAN_NAMES[pass]);
-    hipLaunchKernelGGL(k_wp_scan_local, dim3(nblk), dim3(S_THREADS), 0, ctx->stream, hist, cells, bsum);
-    hipLaunchKernelGGL(k_wp_scan_one<false>, dim3(1), dim3(S_THREADS), 0, ctx->stream, bsum, nblk);
-    hipLaunchKernelGGL(k_wp_scan_add, dim3(wp_grid(cells)), dim3(256), 0, ctx->stream, hist, cells,
-                       (const uint32_t*)bsum);
+    if ((rc = device_excl_scan(ctx, hist, cells, hist, bsum))) return rc;  // hist[cells]: the total, unused
   }
   {
     ProfScope ps(ctx, SCATTER_NAMES[pass]);
@@ -386,8 +299,9 @@ int link(gm_ctx* ctx, const uint32_t* pos, const uint32_t* keys, uint32_t N, OUT
   ProfScope ps(ctx, "wires_perm_link");
   hipLaunchKernelGGL(k_wp_link<OUT>, dim3(ltiles), dim3(WP_LINK_TPB), 0, ctx->stream, pos, keys, N, out,
                      last_head, deferred);
-  hipLaunchKernelGGL(k_wp_scan_one<true>, dim3(1), dim3(S_THREADS), 0, ctx->stream, last_head, ltiles);
-  hipLaunchKernelGGL(k_wp_link_fix<OUT>, dim3(wp_grid(ltiles)), dim3(256), 0, ctx->stream, pos,
+  int rc;
+  if ((rc = block_scan_inplace(ctx, last_head, ltiles, true))) return rc;
+  hipLaunchKernelGGL(k_wp_link_fix<OUT>, dim3(grid_for(ltiles)), dim3(256), 0, ctx->stream, pos,
                      (const uint32_t*)last_head, (const uint32_t*)deferred, ltiles, out);
   GM_HIP(hipGetLastError());
   return GM_OK;
@@ -405,20 +319,19 @@ int plonk_wires_perm_queue(gm_ctx* ctx, Arena& arena, const gm_plonk_wires* w, i
   const uint32_t tiles = (N + WP_TILE - 1) / WP_TILE;
   const uint32_t ltiles = (N + WP_LINK_TPB - 1) / WP_LINK_TPB;
   const size_t cells = (size_t)WP_DIGITS * tiles;
-  const size_t nblk = (cells + WP_SCAN_BLK - 1) / WP_SCAN_BLK;
   int rc;
   DevBuf pos[2], key[2], hist, bsum, lh, df;
   for (int k = 0; k < 2; k++) {
     if ((rc = pos[k].alloc(arena, sizeof(uint32_t) * N))) return rc;
     if ((rc = key[k].alloc(arena, sizeof(uint32_t) * N))) return rc;
   }
-  if ((rc = hist.alloc(arena, sizeof(uint32_t) * cells))) return rc;
-  if ((rc = bsum.alloc(arena, sizeof(uint32_t) * nblk))) return rc;
+  if ((rc = hist.alloc(arena, sizeof(uint32_t) * (cells + 1)))) return rc;
+  if ((rc = bsum.alloc(arena, sizeof(uint32_t) * scan_ws_words(cells)))) return rc;
   if ((rc = lh.alloc(arena, sizeof(uint32_t) * ltiles))) return rc;
   if ((rc = df.alloc(arena, sizeof(uint32_t) * ltiles))) return rc;
   int cur = 0;  // pos[cur] holds the sorted order
   if (passes == 0) {
-    hipLaunchKernelGGL(k_wp_iota, dim3(wp_grid(N)), dim3(256), 0, ctx->stream, pos[0].as<uint32_t>(), N);
+    hipLaunchKernelGGL(k_wp_iota, dim3(grid_for(N)), dim3(256), 0, ctx->stream, pos[0].as<uint32_t>(), N);
     GM_HIP(hipMemsetAsync(key[0].p, 0, sizeof(uint32_t) * N, ctx->stream));  // the one wire is 0
     GM_HIP(hipGetLastError());
   }
@@ -439,7 +352,7 @@ int plonk_wires_perm_queue(gm_ctx* ctx, Arena& arena, const gm_plonk_wires* w, i
     if ((rc = link<uint32_t>(ctx, sorted, skeys, N, o, lh.as<uint32_t>(), df.as<uint32_t>()))) return rc;
     *out32 = o;
     if (out64) {
-      hipLaunchKernelGGL(k_wp_widen<int64_t>, dim3(wp_grid(N)), dim3(256), 0, ctx->stream, (const uint32_t*)o, N,
+      hipLaunchKernelGGL(k_wp_widen<int64_t>, dim3(grid_for(N)), dim3(256), 0, ctx->stream, (const uint32_t*)o, N,
                          out64);
       GM_HIP(hipGetLastError());
     }

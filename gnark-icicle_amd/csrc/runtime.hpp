@@ -462,4 +462,11 @@ struct DevBuf {
 
 inline unsigned blocks_for(size_t n, unsigned tpb) { return (unsigned)((n + tpb - 1) / tpb); }
 
+// The grid of a grid-stride kernel of 256-lane blocks: one lane per item up to
+// 8 blocks on each of 256 CUs, at least one block.
+constexpr unsigned GRID_MAX_BLOCKS = 2048;
+inline unsigned grid_for(size_t lanes) {
+  return (unsigned)std::min<size_t>(std::max<size_t>((lanes + 255) / 256, 1), GRID_MAX_BLOCKS);
+}
+
 }  // namespace gm

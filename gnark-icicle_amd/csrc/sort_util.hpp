@@ -1,6 +1,8 @@
-// Block-level building blocks of the MSM bucket sort (msm_impl.hpp pass 1,
-// msm_sort.hip pass 2): wave / block scans and an LDS counter increment that
-// returns the entry's rank.  All assume 1024-thread blocks of wave64.
+// Block-level building blocks of the counting sorts and scans (the MSM bucket
+// sort in msm_impl.hpp and msm_sort.hip, the wires permutation's radix sort and
+// link, the device-wide scan in scan.hip): wave / block scans of u32, by sum or
+// by max, and an LDS counter increment that returns the entry's rank.  All
+// assume 1024-thread blocks of wave64 unless they say otherwise.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -9,18 +11,55 @@ namespace gm {
 
 constexpr uint32_t S_THREADS = 1024;
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
+// the scans' operator: sum mod 2^32, or max (identity 0 for both)
+template <bool MAX>
+__device__ __forceinline__ uint32_t scan_op(uint32_t a, uint32_t b) {
+  return MAX ? max(a, b) : a + b;
+}
+
+// inclusive scan over the wave (any block size)
+template <bool MAX>
+__device__ __forceinline__ uint32_t wave_incl(uint32_t v) {
   const uint32_t lane = threadIdx.x & 63;
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
     const uint32_t u = __shfl_up(v, d, 64);
-    if (lane >= (uint32_t)d) v += u;
+    if (lane >= (uint32_t)d) v = scan_op<MAX>(v, u);
   }
   return v;
 }
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) { return wave_incl<false>(v); }
 
-// Exclusive scan of a[0, len) (LDS) by a 1024-thread block; returns the total.
-// wsum: 17 words of LDS.  Synchronises on entry and exit.
+// Exclusive scan (sum, or max with identity 0) of one value per thread over a
+// 1024-thread block; *total receives the block's result.  ws: 17 words of LDS.
+// Synchronises on entry and exit.
+template <bool MAX>
+__device__ __forceinline__ uint32_t block_excl(uint32_t v, uint32_t* ws, uint32_t* total) {
+  __syncthreads();
+  const uint32_t t = threadIdx.x, lane = t & 63;
+  const uint32_t inc = wave_incl<MAX>(v);
+  uint32_t exc = __shfl_up(inc, 1, 64);
+  if (lane == 0) exc = 0;
+  if (lane == 63) ws[t >> 6] = inc;
+  __syncthreads();
+  if (t < 64) {
+    const uint32_t x = t < 16 ? ws[t] : 0u;
+    const uint32_t xi = wave_incl<MAX>(x);
+    uint32_t xe = __shfl_up(xi, 1, 64);
+    if (t == 0) xe = 0;
+    if (t < 16) ws[t] = xe;
+    if (t == 15) ws[16] = xi;
+  }
+  __syncthreads();
+  const uint32_t r = scan_op<MAX>(ws[t >> 6], exc);
+  *total = ws[16];
+  __syncthreads();
+  return r;
+}
+
+// Exclusive sum scan of a[0, len) (LDS) by a 1024-thread block; returns the total.
+// wsum: 17 words of LDS.  Synchronises on entry and exit.  (Not written over
+// block_excl: the MSM sort's kernels would change their register use.)
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t* a, uint32_t len, uint32_t* wsum) {
   __syncthreads();
   const uint32_t t = threadIdx.x;

@@ -9,6 +9,7 @@
 #include "msm.hpp"
 #include "pair_fp2.hpp"
 #include "runtime.hpp"
+#include "scan.hpp"
 #include "../../include/gnark_mi355x_testhooks.h"
 
 namespace gm {
@@ -518,6 +519,30 @@ extern "C" int gm_test_msm_g2_keyless_plan(gm_ctx* ctx, int curve, const void* s
   gm::CtxLock g(ctx);
   GM_HIP(hipSetDevice(ctx->device));
   return GM_CURVE(curve, g2_keyless_plan_t<C>(ctx, scalars_dev, points_dev, n));
+}
+
+// The u32 scans of scan.hpp on their own.  op 0: device_excl_scan (out_dev may be
+// in_dev; the workspace holds 0xFF bytes going in); op 1: the one-block max scan
+// over a copy of the input in out_dev.
+extern "C" int gm_test_scan(gm_ctx* ctx, int op, const void* in_dev, size_t n, void* out_dev) {
+  if (!ctx || !out_dev || (n && !in_dev) || op < 0 || op > 1 || (op == 1 && n > 0xffffffffu)) return GM_ERR_INVALID;
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  gm::Arena arena(ctx);
+  int rc;
+  if (op == 0) {
+    gm::DevBuf ws;
+    const size_t bytes = sizeof(uint32_t) * gm::scan_ws_words(n);
+    if ((rc = ws.alloc(arena, bytes))) return rc;
+    if (bytes) GM_HIP(hipMemsetAsync(ws.p, 0xFF, bytes, ctx->stream));
+    rc = gm::device_excl_scan(ctx, (const uint32_t*)in_dev, n, (uint32_t*)out_dev, ws.as<uint32_t>());
+  } else {
+    if (n && out_dev != in_dev)
+      GM_HIP(hipMemcpyAsync(out_dev, in_dev, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, ctx->stream));
+    rc = gm::block_scan_inplace(ctx, (uint32_t*)out_dev, (uint32_t)n, true);
+  }
+  GM_HIP(hipStreamSynchronize(ctx->stream));  // before the arena is released
+  return rc;
 }
 
 // The geometry of an MSM from the driver's own host functions (msm.hpp): no

@@ -70,7 +70,7 @@ SYMBOLS = [
 # test-only library (include/gnark_mi355x_testhooks.h, libgnark_mi355x_testhooks.so)
 TEST_SYMBOLS = ["gm_test_field_op", "gm_test_point_op", "gm_test_stage_replay_chain",
                 "gm_test_msm_g2_keyless_plan", "gm_test_field_raw_op", "gm_test_point_raw_op",
-                "gm_test_msm_geometry"]
+                "gm_test_msm_geometry", "gm_test_scan"]
 TESTHOOKS_PATH = os.path.join(os.path.dirname(LIB_PATH), "libgnark_mi355x_testhooks.so")
 
 
@@ -230,6 +230,7 @@ def load_testhooks(path: str = None):
     T.gm_test_field_raw_op.argtypes = [vp, i, i, i, i, vp, vp, vp, vp, vp, sz]
     T.gm_test_point_raw_op.argtypes = [vp, i, i, i, i, vp, vp, vp, vp, sz]
     T.gm_test_msm_geometry.argtypes = [i, i, sz, i, i, ctypes.POINTER(_MsmGeom)]
+    T.gm_test_scan.argtypes = [vp, i, vp, sz, vp]
     _testhooks = T
     return T
 
@@ -925,6 +926,20 @@ class Context:
         """A G2 launch over a plan built without sorted keys: the launch must refuse
         it, so this raises GmError naming the missing keys."""
         _check(load_testhooks().gm_test_msm_g2_keyless_plan(self.handle, curve_id(curve), scalars.ptr, points.ptr, n))
+
+    def test_scan(self, op: int, out_init, n: int, data=None) -> bytes:
+        """gm_test_scan over n u32.  The output buffer starts as out_init (u32: room
+        for the result and the caller's guard words) and comes back whole.  data:
+        the n input words, or None to scan in place on out_init's first n words."""
+        O = self.copy_to_device(np.ascontiguousarray(out_init, dtype=np.uint32))
+        I = self.copy_to_device(np.ascontiguousarray(data, dtype=np.uint32)) if data is not None and n else None
+        try:
+            _check(load_testhooks().gm_test_scan(self.handle, op, I.ptr if I else O.ptr, n, O.ptr))
+            return O.to_host()
+        finally:
+            for x in (I, O):
+                if x:
+                    x.free()
 
 
 # ---------------------------------------------------------------------------

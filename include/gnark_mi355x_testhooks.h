@@ -91,6 +91,13 @@ int gm_test_stage_replay_chain(gm_g16_stage* st, const void* wires, size_t nb_in
  * holds n G2 points; nothing reads them when the launch refuses. */
 int gm_test_msm_g2_keyless_plan(gm_ctx* ctx, int curve, const void* scalars_dev, const void* points_dev, size_t n);
 
+/* The device-wide u32 scans (csrc/scan.hpp) on their own, arrays of u32 on the
+ * device.  op 0: the exclusive sum scan of in_dev[0, n) into out_dev[0, n], the
+ * total in out_dev[n]; out_dev may be in_dev; the workspace comes from the arena
+ * and is filled with 0xFF bytes first.  op 1: in_dev[0, n) is copied to out_dev
+ * and becomes its exclusive running maximum (from 0) in place, by one block. */
+int gm_test_scan(gm_ctx* ctx, int op, const void* in_dev, size_t n, void* out_dev);
+
 /* Host-only report of the geometry an MSM of n scalars derives from its sizes:
  * the functions the driver itself calls (msm.hpp msm_plan_geom, msm_seg_geom,
  * msm_tree_geom), with no context and no device.  c_override is the window as
