@@ -21,6 +21,7 @@
 #include "plonk_scs.hpp"
 #include "plonk_wires.hpp"
 #include "plonk_wires_perm.hpp"
+#include "points_check.hpp"
 #include "msm.hpp"
 #include "ntt.hpp"
 #include "runtime.hpp"
@@ -1307,6 +1308,37 @@ int gm_batch_mul_base(gm_ctx* ctx, int curve, int g2, const void* base, const vo
   GM_HIP(hipSetDevice(ctx->device));
   return GM_CURVE01(curve, g2 ? batch_mul_t<C, true>(ctx, base, sc, n, out)
                                : batch_mul_t<C, false>(ctx, base, sc, n, out));
+}
+
+// ---- point validation (points_check.hip; the streamed entries: pk_io.hip) -------------
+int gm_points_check(gm_ctx* ctx, int curve, int g2, const void* points_dev, size_t n, uint8_t* status_dev,
+                    gm_points_report* out) {
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_points_check")) return rc;
+  if (!ctx || !out || (n && !points_dev)) return refuse_null("gm_points_check");
+  if (g2 != 0 && g2 != 1) {
+    set_error("gm_points_check: g2 must be 0 or 1");
+    return GM_ERR_INVALID;
+  }
+  if ((uintptr_t)points_dev % 16) {
+    set_error("gm_points_check: the points must be 16-byte aligned");
+    return GM_ERR_INVALID;
+  }
+  if (n == 0) {
+    points_report_zero(out, 0);
+    return GM_OK;
+  }
+  return points_check_device(ctx, curve, g2 != 0, points_dev, n, status_dev, out);
+}
+
+int gm_set_points_check_chunk(gm_ctx* ctx, size_t bytes) {
+  if (!ctx) return refuse_null("gm_set_points_check_chunk");
+  if (bytes > POINTS_CHECK_CHUNK_MAX) {
+    set_error("gm_set_points_check_chunk: bytes must be 0 (the default) or at most 64 MiB");
+    return GM_ERR_INVALID;
+  }
+  gm::CtxLock g(ctx);
+  ctx->points_check_chunk = bytes;
+  return GM_OK;
 }
 
 // ---- Groth16 setup: fixed-base batch multiplication (g16_setup.hip) --------------------

@@ -26,6 +26,7 @@
 #include "curves.hpp"
 #include "groth16.hpp"
 #include "msm.hpp"
+#include "points_check.hpp"
 #include "runtime.hpp"
 
 using namespace gm;
@@ -85,13 +86,13 @@ struct IoRing {
   void* dev[2] = {nullptr, nullptr};
   hipEvent_t ev[2] = {nullptr, nullptr};
   bool used[2] = {false, false};
-  int init(bool want_dev) {
+  int init(bool want_dev, size_t cap = IO_CHUNK) {
     for (int i = 0; i < 2; i++) {
-      if (hipHostMalloc(&host[i], IO_CHUNK, hipHostMallocDefault) != hipSuccess) {
+      if (hipHostMalloc(&host[i], cap, hipHostMallocDefault) != hipSuccess) {
         set_error("pk io: hipHostMalloc failed");
         return GM_ERR_OOM;
       }
-      if (want_dev && hipMalloc(&dev[i], IO_CHUNK) != hipSuccess) {
+      if (want_dev && hipMalloc(&dev[i], cap) != hipSuccess) {
         set_error("pk io: hipMalloc failed");
         return GM_ERR_OOM;
       }
@@ -365,6 +366,164 @@ int gm_g16_pk_upload_dump_shard(gm_ctx* ctx, int curve, const gm_g16_pk_host* me
 int gm_g16_pk_upload_dump(gm_ctx* ctx, int curve, const gm_g16_pk_host* meta, int fd, uint64_t offset,
                           unsigned flags, uint64_t* end_offset, gm_g16_pk** out) {
   return gm_g16_pk_upload_dump_shard(ctx, curve, meta, fd, offset, flags, 0, 1, end_offset, out);
+}
+
+// ---- streamed point validation (points_check.hip) -----------------------------
+}  // extern "C"
+
+namespace {
+
+int check_refuse(const char* entry, const char* what) {
+  set_error(std::string(entry) + ": " + what);
+  return GM_ERR_INVALID;
+}
+
+// One call's streamed checks: the arrays go through the loader's two-slot pinned
+// ring, chunk by chunk, and leave nothing on the device but the result words.
+struct CheckStream {
+  gm_ctx* ctx;
+  int curve;
+  size_t chunk;
+  IoRing ring;
+  Arena arena;
+  DevBuf res;
+  size_t k = 0;
+  CheckStream(gm_ctx* c, int cv)
+      : ctx(c), curve(cv), chunk(c->points_check_chunk ? c->points_check_chunk : POINTS_CHECK_CHUNK), arena(c) {}
+  // Lanes of one device-filling round at one wave per SIMD, the occupancy of all
+  // the ladder kernels: the chunks' kernels run one after
+  // another on the stream, so a chunk that is not a whole number of rounds ends in
+  // a partly filled one (16 MiB of BLS12-377 G2 points are 1.33 rounds: the
+  // kernels of a 2^22 array summed to 304 ms against 195 ms for one launch).
+  size_t round_lanes = 0;
+  // largest: the byte size of the call's largest array
+  int init(size_t largest) {
+    int cus = 0;
+    GM_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    round_lanes = (size_t)std::max(cus, 1) * 4 * 64;
+    const size_t cap = std::max(std::min(chunk, largest), 4 * fp_bytes(curve));
+    if (int rc = ring.init(true, cap)) return rc;
+    return res.alloc(arena, PC_RES_WORDS * sizeof(unsigned long long));
+  }
+  // `count` points from host memory (src) or, with src == NULL, from fd at off
+  int run(bool g2, const void* src, int fd, uint64_t off, size_t count, gm_points_report* out) {
+    points_report_zero(out, count);
+    if (count == 0) return GM_OK;
+    const size_t pb = 2 * (g2 ? 2 : 1) * fp_bytes(curve);
+    size_t per = std::max<size_t>(chunk / pb, 1);
+    if (per > round_lanes) per -= per % round_lanes;  // whole rounds per chunk
+    unsigned long long* r = res.as<unsigned long long>();
+    int rc;
+    if ((rc = points_check_reset(ctx, r))) return rc;
+    for (size_t i0 = 0; i0 < count; i0 += per, k ^= 1) {
+      const size_t cnt = std::min(per, count - i0);
+      if ((rc = ring.acquire((int)k))) return rc;
+      if (src)
+        par_memcpy(ring.host[k], (const char*)src + i0 * pb, cnt * pb, H2D_FILL_THREADS);
+      else if ((rc = read_at(fd, ring.host[k], cnt * pb, off + i0 * pb)))
+        return rc;
+      GM_HIP(hipMemcpyAsync(ring.dev[k], ring.host[k], cnt * pb, hipMemcpyHostToDevice, ctx->stream));
+      if ((rc = points_check_queue(ctx, curve, g2, ring.dev[k], cnt, i0, nullptr, r))) return rc;
+      GM_HIP(hipEventRecord(ring.ev[k], ctx->stream));
+    }
+    return points_check_read(ctx, r, count, out);
+  }
+};
+
+void pk_report_close(gm_g16_pk_report* out) {
+  out->first_bad_member = -1;
+  for (int m = GM_G16_PK_MEMBERS - 1; m >= 0; m--)
+    if (out->member[m].first_bad != out->member[m].n) out->first_bad_member = m;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gm_points_check_host(gm_ctx* ctx, int curve, int g2, const void* points_host, size_t n, gm_points_report* out) {
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_points_check_host")) return rc;
+  if (!ctx || !out || (n && !points_host)) return check_refuse("gm_points_check_host", "a required pointer is NULL");
+  if (g2 != 0 && g2 != 1) return check_refuse("gm_points_check_host", "g2 must be 0 or 1");
+  const size_t pb = 2 * (g2 ? 2 : 1) * fp_bytes(curve);
+  if (n > (~size_t(0)) / pb) return check_refuse("gm_points_check_host", "n points do not fit the address space");
+  if (n == 0) {
+    points_report_zero(out, 0);
+    return GM_OK;
+  }
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  CheckStream cs(ctx, curve);
+  if (int rc = cs.init(n * pb)) return rc;
+  return cs.run(g2 != 0, points_host, -1, 0, n, out);
+}
+
+int gm_g16_pk_check(gm_ctx* ctx, int curve, const gm_g16_pk_host* pk, gm_g16_pk_report* out) {
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_g16_pk_check")) return rc;
+  if (!ctx || !pk || !out) return check_refuse("gm_g16_pk_check", "a required pointer is NULL");
+  if (pk->domain_size < 2) return check_refuse("gm_g16_pk_check", "domain_size must be at least 2");
+  struct {
+    const void* p;
+    size_t n;
+    bool g2;
+  } const mem[GM_G16_PK_MEMBERS] = {
+      {pk->g1_alpha, 1, false}, {pk->g1_beta, 1, false},   {pk->g1_delta, 1, false},
+      {pk->g2_beta, 1, true},   {pk->g2_delta, 1, true},   {pk->g1_A, pk->nbA, false},
+      {pk->g1_B, pk->nbB, false}, {pk->g1_Z, pk->domain_size - 1, false}, {pk->g1_K, pk->nbK, false},
+      {pk->g2_B, pk->nbB, true}};
+  const size_t fb = fp_bytes(curve);
+  size_t largest = 0;
+  for (const auto& m : mem) {
+    if (m.n && !m.p) return check_refuse("gm_g16_pk_check", "a point array of the key is NULL");
+    const size_t pb = 2 * (m.g2 ? 2 : 1) * fb;
+    if (m.n > (~size_t(0)) / pb) return check_refuse("gm_g16_pk_check", "an array does not fit the address space");
+    largest = std::max(largest, m.n * pb);
+  }
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  CheckStream cs(ctx, curve);
+  if (int rc = cs.init(largest)) return rc;
+  for (int m = 0; m < GM_G16_PK_MEMBERS; m++)
+    if (int rc = cs.run(mem[m].g2, mem[m].p, -1, 0, mem[m].n, &out->member[m])) return rc;
+  pk_report_close(out);
+  return GM_OK;
+}
+
+int gm_g16_pk_check_dump(gm_ctx* ctx, int curve, const gm_g16_pk_host* meta, int fd, uint64_t offset,
+                         gm_g16_pk_report* out, uint64_t* end_offset) {
+  if (int rc = check_curve(curve, CURVES_01, "gm_g16_pk_check_dump")) return rc;
+  if (!ctx || !meta || !out) return check_refuse("gm_g16_pk_check_dump", "a required pointer is NULL");
+  if (fd < 0) return check_refuse("gm_g16_pk_check_dump", "bad file descriptor");
+  if (meta->domain_size < 2) return check_refuse("gm_g16_pk_check_dump", "domain_size must be at least 2");
+  // slice table, as gm_g16_pk_upload_dump_shard reads it
+  const size_t expect[5] = {meta->nbA, meta->nbB, meta->domain_size - 1, meta->nbK, meta->nbB};
+  uint64_t pos[5];
+  uint64_t off = offset;
+  size_t largest = 0;
+  for (int a = 0; a < 5; a++) {
+    uint64_t cnt = 0;
+    uint8_t le[8];
+    if (int rc = read_at(fd, le, 8, off)) return rc;
+    for (int b = 7; b >= 0; b--) cnt = (cnt << 8) | le[b];
+    if (cnt != expect[a]) {
+      set_error("pk dump: slice " + std::to_string(a) + " holds " + std::to_string(cnt) + " points, expected " +
+                std::to_string(expect[a]));
+      return GM_ERR_INVALID;
+    }
+    pos[a] = off + 8;
+    const size_t bytes = cnt * 2 * (a == PK_B2 ? 2 : 1) * fp_bytes(curve);
+    largest = std::max(largest, bytes);
+    off = pos[a] + bytes;
+  }
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  CheckStream cs(ctx, curve);
+  if (int rc = cs.init(largest)) return rc;
+  for (int m = 0; m < GM_G16_PK_G1_A; m++) points_report_zero(&out->member[m], 0);
+  for (int a = 0; a < 5; a++)
+    if (int rc = cs.run(a == PK_B2, nullptr, fd, pos[a], expect[a], &out->member[GM_G16_PK_G1_A + a])) return rc;
+  pk_report_close(out);
+  if (end_offset) *end_offset = off;
+  return GM_OK;
 }
 
 int gm_g16_pk_save_cache(gm_ctx* ctx, const gm_g16_pk* pk, int fd) {

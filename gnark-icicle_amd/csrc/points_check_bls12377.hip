@@ -1,0 +1,6 @@
+// Point check, BLS12-377: the G1 and G2 instantiations of points_check_impl.hpp.
+#include "points_check_impl.hpp"
+
+namespace gm {
+GM_PC_INSTANTIATE(CurveBLS12377)
+}  // namespace gm

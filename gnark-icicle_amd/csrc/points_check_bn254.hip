@@ -1,0 +1,6 @@
+// Point check, BN254: the G1 and G2 instantiations of points_check_impl.hpp.
+#include "points_check_impl.hpp"
+
+namespace gm {
+GM_PC_INSTANTIATE(CurveBN254)
+}  // namespace gm

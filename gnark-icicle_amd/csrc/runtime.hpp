@@ -86,6 +86,7 @@ struct gm_ctx {
   int msm_piece_len = 0;  // G1 piece length T (gm_set_msm_piece_len): 0 = the size rule
   int fixed_base_c = 0;   // window of gm_batch_mul_fixed (gm_set_fixed_base_window): 0 = the model
   int g16_column_cut = 0; // column length split over blocks in gm_g16_setup (gm_set_g16_setup_column_cut): 0 = default
+  size_t points_check_chunk = 0;  // chunk bytes of the streamed point checks (gm_set_points_check_chunk): 0 = default
   // workspace arena (stack-discipline scopes), plus two more for MSMs whose host
   // tail is deferred (pipelined MSMs: gm_msm_async, the Groth16 MSM sequence)
   gm::ArenaState arena;

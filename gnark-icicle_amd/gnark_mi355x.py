@@ -66,6 +66,8 @@ SYMBOLS = [
     "gm_plonk_scs_selector", "gm_plonk_pk_setup_scs", "gm_plonk_scs_check",
     "gm_set_fixed_base_window", "gm_batch_mul_fixed",
     "gm_set_g16_setup_column_cut", "gm_g16_setup_sizes", "gm_g16_setup", "gm_g16_pk_setup",
+    "gm_points_check", "gm_points_check_host", "gm_set_points_check_chunk", "gm_g16_pk_check",
+    "gm_g16_pk_check_dump",
 ]
 # test-only library (include/gnark_mi355x_testhooks.h, libgnark_mi355x_testhooks.so)
 TEST_SYMBOLS = ["gm_test_field_op", "gm_test_point_op", "gm_test_stage_replay_chain",
@@ -195,6 +197,29 @@ class _G16SetupOut(ctypes.Structure):
 
 # gm_test_msm_geometry layouts (include/gnark_mi355x_testhooks.h)
 TGEOM_PLAIN, TGEOM_GLV, TGEOM_PRECOMP, TGEOM_DEFAULT = 0, 1, 2, 3
+# point validation (gm_points_check*): the class of a point, the first that applies
+POINT_OK, POINT_NOT_REDUCED, POINT_OFF_CURVE, POINT_OFF_SUBGROUP = 0, 1, 2, 3
+# the members of a Groth16 key in gm_g16_pk_report order
+G16_PK_MEMBERS = ("g1_alpha", "g1_beta", "g1_delta", "g2_beta", "g2_delta", "g1_A", "g1_B", "g1_Z", "g1_K", "g2_B")
+
+
+class _PointsReport(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in ("n", "infinities", "not_reduced", "off_curve", "off_subgroup",
+                                               "first_bad")] + [("first_class", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class _G16PkReport(ctypes.Structure):
+    _fields_ = [("member", _PointsReport * len(G16_PK_MEMBERS)), ("first_bad_member", ctypes.c_int32)]
+
+    def as_dict(self) -> dict:
+        out = {name: self.member[i].as_dict() for i, name in enumerate(G16_PK_MEMBERS)}
+        out["first_bad_member"] = None if self.first_bad_member < 0 else G16_PK_MEMBERS[self.first_bad_member]
+        return out
+
+
 TGEOM_MAX_LEVELS = 24
 
 
@@ -365,6 +390,11 @@ def load_library(path: str = LIB_PATH):
     L.gm_g16_setup.argtypes = [vp, vp, ctypes.POINTER(_G16SetupIn), ctypes.POINTER(_G16SetupOut)]
     L.gm_g16_pk_setup.argtypes = [vp, vp, ctypes.POINTER(_G16SetupIn), ctypes.c_uint, pvp,
                                   ctypes.POINTER(_G16SetupOut)]
+    L.gm_points_check.argtypes = [vp, i, i, vp, sz, vp, ctypes.POINTER(_PointsReport)]
+    L.gm_points_check_host.argtypes = [vp, i, i, vp, sz, ctypes.POINTER(_PointsReport)]
+    L.gm_set_points_check_chunk.argtypes = [vp, sz]
+    L.gm_g16_pk_check.argtypes = [vp, i, vp, ctypes.POINTER(_G16PkReport)]
+    L.gm_g16_pk_check_dump.argtypes = [vp, i, vp, i, u64, ctypes.POINTER(_G16PkReport), ctypes.POINTER(u64)]
     _lib = L
     return L
 
@@ -501,6 +531,57 @@ class Context:
 
     def free_device_pointer(self, buf: DeviceBuffer):
         buf.free()
+
+    # ---- point validation --------------------------------------------------
+    def points_check(self, curve, points: DeviceBuffer, n: int, g2: bool = False, status: bool = False):
+        """gm_points_check over n device-resident gnark points: the report as a
+        dict, and with status=True also the class byte of every point."""
+        rep = _PointsReport()
+        st = self.malloc(max(n, 1)) if status else None
+        try:
+            _check(load_library().gm_points_check(self.handle, curve_id(curve), int(g2), points.ptr, n,
+                                                  st.ptr if st else None, ctypes.byref(rep)))
+            if st is None:
+                return rep.as_dict()
+            return rep.as_dict(), np.frombuffer(st.to_host(n), np.uint8)
+        finally:
+            if st is not None:
+                st.free()
+
+    def points_check_host(self, curve, points, g2: bool = False) -> dict:
+        """gm_points_check_host: gnark points in host memory, streamed in chunks."""
+        a = _buf(points)
+        rep = _PointsReport()
+        _check(load_library().gm_points_check_host(self.handle, curve_id(curve), int(g2), _p(a),
+                                                   a.size // point_bytes(curve, g2), ctypes.byref(rep)))
+        return rep.as_dict()
+
+    def set_points_check_chunk(self, nbytes: int):
+        """Test knob: the chunk of the streamed point checks (0 = the default)."""
+        _check(load_library().gm_set_points_check_chunk(self.handle, nbytes))
+
+    def g16_pk_check(self, curve, pk: dict, domain_size: int, nb_wires: int, nb_public: int) -> dict:
+        """gm_g16_pk_check: one report per member of the key ProvingKey would upload."""
+        h, arrs = _pk_host_struct(curve, pk, domain_size, nb_wires, nb_public)
+        rep = _G16PkReport()
+        _check(load_library().gm_g16_pk_check(self.handle, curve_id(curve), ctypes.byref(h), ctypes.byref(rep)))
+        del arrs
+        return rep.as_dict()
+
+    def g16_pk_check_dump(self, curve, path: str, offset: int, counts, domain_size: int):
+        """gm_g16_pk_check_dump: the five point slices of a WriteDump file from byte
+        `offset`; counts = (nbA, nbB, nbK).  Returns (report, end_offset)."""
+        h = _PkHost()
+        h.domain_size = domain_size
+        h.nbA, h.nbB, h.nbK = counts
+        rep, end = _G16PkReport(), ctypes.c_uint64()
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            _check(load_library().gm_g16_pk_check_dump(self.handle, curve_id(curve), ctypes.byref(h), fd, offset,
+                                                       ctypes.byref(rep), ctypes.byref(end)))
+        finally:
+            os.close(fd)
+        return rep.as_dict(), end.value
 
     def synchronize(self):
         _check(load_library().gm_synchronize(self.handle))

@@ -42,9 +42,12 @@ typedef enum {
 /* Curve ids.  BN254 and BLS12-377 are served by every entry that takes a curve.
  * BLS12-381 (Fp 381 bits = 6 x u64, Fr 255 bits = 4 x u64, G1 96 B, G2 192 B) is
  * served by the host group helpers, the point uploads, every MSM entry, the NTT /
- * poly-ops / computeH calls, the KZG commit / open calls and the Groth16 key
+ * poly-ops / computeH calls, the KZG commit / open calls, the Groth16 key
  * upload and prover (gm_g16_pk_upload[_ex], gm_g16_prove[_device], gm_g16_finish,
- * gm_g16_partial_bytes).  Every other entry that takes a curve -- the PLONK calls
+ * gm_g16_partial_bytes) and the point validation of what those uploads take
+ * (gm_points_check, gm_points_check_host, gm_g16_pk_check; gm_g16_pk_check_dump
+ * stands with the dump loader below).  Every other entry that takes a curve --
+ * the PLONK calls
  * and gm_kzg_srs_lagrange, gm_r1cs_upload and what needs it (gm_g16_prove_r1cs,
  * gm_g16_setup*, gm_g16_pk_setup), gm_batch_mul_fixed / gm_batch_mul_base, the
  * key dump / cache loaders, gm_g16_pk_upload_shard / _multi, gm_g16_prove_partial,
@@ -938,6 +941,64 @@ int gm_g16_pk_upload_dump_shard(gm_ctx* ctx, int curve, const gm_g16_pk_host* me
  * SURVEY.md §5's checkpoint row). */
 int gm_g16_pk_save_cache(gm_ctx* ctx, const gm_g16_pk* pk, int fd);
 int gm_g16_pk_load_cache(gm_ctx* ctx, int fd, gm_g16_pk** out);
+
+/* ---- point validation: curve and subgroup checks on the device -----------
+ * Every upload entry takes raw Montgomery limbs unchecked, as gnark's
+ * UnsafeReadFrom / ReadDump do (backend/groth16/bn254/marshal.go:320-324,
+ * :386-389, :458-460); ProvingKey.ReadFrom (:314-318) pays gnark-crypto's
+ * IsInSubGroup per point on the CPU.  These entries class every point of a
+ * gnark-layout array on the device, one lane per point.  The first class that
+ * applies wins:
+ *   GM_POINT_OK            the point passes; (0, 0), gnark's affine infinity, is OK
+ *                          and is also counted in `infinities`
+ *   GM_POINT_NOT_REDUCED   a coordinate (or an Fp2 component) is >= p as stored;
+ *                          no arithmetic is done on it; (0, p) is this class
+ *   GM_POINT_OFF_CURVE     y^2 != x^3 + b (G2: the twist's b')
+ *   GM_POINT_OFF_SUBGROUP  on the curve and [r]P != infinity
+ * for every input, by endomorphism equations equivalent to [r]P = infinity
+ * (DESIGN.md section 3.9).  All entries return GM_OK when the check ran, whatever
+ * it found: the report carries the verdict.  first_bad is the lowest failing
+ * index (n if none) and first_class its class.  n = 0 gives a zero report.
+ * GM_ERR_INVALID, before any launch: a NULL context, array (with n > 0) or
+ * report, g2 outside {0, 1}, a device array that is not 16-byte aligned, a bad
+ * fd, an unknown curve id.  Curve ids 0, 1 and 2, except gm_g16_pk_check_dump:
+ * ids 0 and 1 (GM_ERR_UNSUPPORTED for 2, like gm_g16_pk_upload_dump). */
+enum { GM_POINT_OK = 0, GM_POINT_NOT_REDUCED = 1, GM_POINT_OFF_CURVE = 2, GM_POINT_OFF_SUBGROUP = 3 };
+typedef struct {
+  uint64_t n, infinities, not_reduced, off_curve, off_subgroup, first_bad /* n if none */;
+  uint32_t first_class;
+} gm_points_report;
+/* points_dev: n gnark affine points on the device (what gm_copy_points_to_device
+ * leaves there).  status_dev: NULL, or n bytes on the device that receive each
+ * point's class. */
+int gm_points_check(gm_ctx* ctx, int curve, int g2, const void* points_dev, size_t n,
+                    uint8_t* status_dev /* NULL or n bytes */, gm_points_report* out);
+/* The same over host memory, streamed through the pinned chunk ring of the dump
+ * loader: nothing stays on the device, so any n works. */
+int gm_points_check_host(gm_ctx* ctx, int curve, int g2, const void* points_host, size_t n, gm_points_report* out);
+/* Test knob: the chunk of gm_points_check_host, gm_g16_pk_check and
+ * gm_g16_pk_check_dump in bytes (0 = the default, 16 MiB; at most 64 MiB, the dump
+ * loader's; a chunk holds at least one point). */
+int gm_set_points_check_chunk(gm_ctx* ctx, size_t bytes);
+/* The ten members of a Groth16 proving key, in report order. */
+enum {
+  GM_G16_PK_G1_ALPHA = 0, GM_G16_PK_G1_BETA, GM_G16_PK_G1_DELTA, GM_G16_PK_G2_BETA, GM_G16_PK_G2_DELTA,
+  GM_G16_PK_G1_A, GM_G16_PK_G1_B, GM_G16_PK_G1_Z, GM_G16_PK_G1_K, GM_G16_PK_G2_B, GM_G16_PK_MEMBERS
+};
+typedef struct {
+  gm_points_report member[GM_G16_PK_MEMBERS];
+  int32_t first_bad_member; /* the first member with a failing point, -1 if none */
+} gm_g16_pk_report;
+/* Checks the points a gm_g16_pk_upload of `pk` would take (counts as there:
+ * nbA, nbB, domain_size - 1, nbK, nbB).  Creates no key. */
+int gm_g16_pk_check(gm_ctx* ctx, int curve, const gm_g16_pk_host* pk, gm_g16_pk_report* out);
+/* Checks the five slices of a WriteDump file the way gm_g16_pk_upload_dump reads
+ * them: the same `offset`, the slice lengths checked against `meta`, the same
+ * *end_offset (may be NULL).  The reports of the five single points stay zero
+ * (the dump's header holds them; check them with gm_points_check_host).  The
+ * file is only read; no key is created. */
+int gm_g16_pk_check_dump(gm_ctx* ctx, int curve, const gm_g16_pk_host* meta, int fd, uint64_t offset,
+                         gm_g16_pk_report* out, uint64_t* end_offset);
 
 /* ---- staged prover inputs --------------------------
  * The R1CS solver (constraint/bn254/solver.go:426-532) makes a, b, c final
