@@ -22,6 +22,7 @@
 #include "plonk_wires.hpp"
 #include "plonk_wires_perm.hpp"
 #include "points_check.hpp"
+#include "points_codec.hpp"
 #include "msm.hpp"
 #include "ntt.hpp"
 #include "runtime.hpp"
@@ -1339,6 +1340,58 @@ int gm_set_points_check_chunk(gm_ctx* ctx, size_t bytes) {
   gm::CtxLock g(ctx);
   ctx->points_check_chunk = bytes;
   return GM_OK;
+}
+
+// ---- point encodings (points_codec.hip; the streamed entry: pk_io.hip) -----------------
+static int codec_refuse(const char* entry, const char* what) {
+  set_error(std::string(entry) + ": " + what);
+  return GM_ERR_INVALID;
+}
+// [a, a + na) and [b, b + nb) share a byte
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return na && nb && x < y + nb && y < x + na;
+}
+
+int gm_points_decode(gm_ctx* ctx, int curve, int g2, int encoding, unsigned flags, const void* enc_dev, size_t n,
+                     void* points_dev, uint8_t* status_dev, gm_points_decode_report* out) {
+  const char* me = "gm_points_decode";
+  if (int rc = check_curve(curve, CURVES_ALL, me)) return rc;
+  if (!ctx || !out || (n && (!enc_dev || !points_dev))) return refuse_null(me);
+  if (g2 != 0 && g2 != 1) return codec_refuse(me, "g2 must be 0 or 1");
+  if (encoding != GM_ENC_COMPRESSED && encoding != GM_ENC_RAW) return codec_refuse(me, "unknown encoding");
+  if (flags & ~GM_DECODE_NO_SUBGROUP_CHECK) return codec_refuse(me, "unknown flags");
+  if ((uintptr_t)enc_dev % 16 || (uintptr_t)points_dev % 16)
+    return codec_refuse(me, "the records and the points must be 16-byte aligned");
+  const size_t rb = codec_record_bytes(curve, g2 != 0, encoding == GM_ENC_RAW), pb = codec_point_bytes(curve, g2 != 0);
+  if (n > (~size_t(0)) / pb) return codec_refuse(me, "n points do not fit the address space");
+  if (ranges_overlap(enc_dev, n * rb, points_dev, n * pb) || ranges_overlap(status_dev, status_dev ? n : 0, points_dev, n * pb) ||
+      ranges_overlap(status_dev, status_dev ? n : 0, enc_dev, n * rb))
+    return codec_refuse(me, "the records, the points and the status bytes must not overlap");
+  if (n == 0) {
+    points_decode_report_zero(out, 0);
+    return GM_OK;
+  }
+  return points_decode_device(ctx, curve, g2 != 0, encoding == GM_ENC_RAW, flags, enc_dev, n, points_dev, status_dev,
+                              out);
+}
+
+int gm_points_encode(gm_ctx* ctx, int curve, int g2, int encoding, const void* points_dev, size_t n, void* enc_dev,
+                     uint64_t* not_reduced) {
+  const char* me = "gm_points_encode";
+  if (int rc = check_curve(curve, CURVES_ALL, me)) return rc;
+  if (!ctx || !not_reduced || (n && (!enc_dev || !points_dev))) return refuse_null(me);
+  if (g2 != 0 && g2 != 1) return codec_refuse(me, "g2 must be 0 or 1");
+  if (encoding != GM_ENC_COMPRESSED && encoding != GM_ENC_RAW) return codec_refuse(me, "unknown encoding");
+  if ((uintptr_t)enc_dev % 16 || (uintptr_t)points_dev % 16)
+    return codec_refuse(me, "the records and the points must be 16-byte aligned");
+  const size_t rb = codec_record_bytes(curve, g2 != 0, encoding == GM_ENC_RAW), pb = codec_point_bytes(curve, g2 != 0);
+  if (n > (~size_t(0)) / pb) return codec_refuse(me, "n points do not fit the address space");
+  if (ranges_overlap(enc_dev, n * rb, points_dev, n * pb))
+    return codec_refuse(me, "the records and the points must not overlap");
+  *not_reduced = 0;
+  if (n == 0) return GM_OK;
+  return points_encode_device(ctx, curve, g2 != 0, encoding == GM_ENC_RAW, points_dev, n, enc_dev, not_reduced);
 }
 
 // ---- Groth16 setup: fixed-base batch multiplication (g16_setup.hip) --------------------

@@ -27,6 +27,7 @@
 #include "groth16.hpp"
 #include "msm.hpp"
 #include "points_check.hpp"
+#include "points_codec.hpp"
 #include "runtime.hpp"
 
 using namespace gm;
@@ -455,6 +456,209 @@ int gm_points_check_host(gm_ctx* ctx, int curve, int g2, const void* points_host
   CheckStream cs(ctx, curve);
   if (int rc = cs.init(n * pb)) return rc;
   return cs.run(g2 != 0, points_host, -1, 0, n, out);
+}
+
+// Records from host memory through the loader's ring: chunk k is copied in and
+// decoded while chunk k + 1 is gathered into the other pinned slot.  The points
+// land in points_dev, or in two chunk-sized scratch buffers when only the host
+// wants them; the copy back to points_host is queued behind each chunk's kernel.
+int gm_points_decode_host(gm_ctx* ctx, int curve, int g2, int encoding, unsigned flags, const void* enc_host,
+                          size_t n, void* points_dev, void* points_host, gm_points_decode_report* out) {
+  const char* me = "gm_points_decode_host";
+  if (int rc = check_curve(curve, CURVES_ALL, me)) return rc;
+  if (!ctx || !out || (n && !enc_host)) return check_refuse(me, "a required pointer is NULL");
+  if (n && !points_dev && !points_host) return check_refuse(me, "points_dev and points_host are both NULL");
+  if (g2 != 0 && g2 != 1) return check_refuse(me, "g2 must be 0 or 1");
+  if (encoding != GM_ENC_COMPRESSED && encoding != GM_ENC_RAW) return check_refuse(me, "unknown encoding");
+  if (flags & ~GM_DECODE_NO_SUBGROUP_CHECK) return check_refuse(me, "unknown flags");
+  if ((uintptr_t)points_dev % 16) return check_refuse(me, "the points must be 16-byte aligned");
+  const bool raw = encoding == GM_ENC_RAW;
+  const size_t rb = codec_record_bytes(curve, g2 != 0, raw), pb = codec_point_bytes(curve, g2 != 0);
+  if (n > (~size_t(0)) / pb) return check_refuse(me, "n points do not fit the address space");
+  if (points_host && n) {
+    const uintptr_t a = (uintptr_t)enc_host, b = (uintptr_t)points_host;
+    if (a < b + n * pb && b < a + n * rb) return check_refuse(me, "the records and the points must not overlap");
+  }
+  points_decode_report_zero(out, n);
+  if (n == 0) return GM_OK;
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  const size_t chunk = ctx->points_check_chunk ? ctx->points_check_chunk : POINTS_CHECK_CHUNK;
+  const size_t per = std::min(std::max<size_t>(chunk / rb, 1), n);
+  IoRing ring;
+  if (int rc = ring.init(true, per * rb)) return rc;
+  Arena arena(ctx);
+  DevBuf res, scratch;
+  if (int rc = res.alloc(arena, CD_RES_WORDS * sizeof(unsigned long long))) return rc;
+  if (!points_dev)
+    if (int rc = scratch.alloc(arena, 2 * per * pb)) return rc;
+  unsigned long long* r = res.as<unsigned long long>();
+  if (int rc = points_decode_reset(ctx, r)) return rc;
+  for (size_t i0 = 0, k = 0; i0 < n; i0 += per, k ^= 1) {
+    const size_t cnt = std::min(per, n - i0);
+    if (int rc = ring.acquire((int)k)) return rc;
+    par_memcpy(ring.host[k], (const char*)enc_host + i0 * rb, cnt * rb, H2D_FILL_THREADS);
+    GM_HIP(hipMemcpyAsync(ring.dev[k], ring.host[k], cnt * rb, hipMemcpyHostToDevice, ctx->stream));
+    char* dst = points_dev ? (char*)points_dev + i0 * pb : scratch.as<char>() + k * per * pb;
+    if (int rc = points_decode_queue(ctx, curve, g2 != 0, raw, flags, ring.dev[k], cnt, i0, dst, nullptr, r)) return rc;
+    if (points_host)
+      GM_HIP(hipMemcpyAsync((char*)points_host + i0 * pb, dst, cnt * pb, hipMemcpyDeviceToHost, ctx->stream));
+    GM_HIP(hipEventRecord(ring.ev[k], ctx->stream));
+  }
+  return points_decode_read(ctx, r, n, out);
+}
+
+int gm_g16_pk_upload_encoded(gm_ctx* ctx, int curve, const gm_g16_pk_host* meta, int fd, uint64_t offset,
+                             int encoding, unsigned flags, void* singles_out, gm_g16_pk_decode_report* report,
+                             uint64_t* end_offset, gm_g16_pk** out) {
+  const char* me = "gm_g16_pk_upload_encoded";
+  if (out) *out = nullptr;
+  if (int rc = check_curve(curve, CURVES_01, me)) return rc;
+  if (!ctx || !meta || !out || !singles_out || !report) return check_refuse(me, "a required pointer is NULL");
+  if (fd < 0) return check_refuse(me, "bad file descriptor");
+  if (meta->domain_size < 2) return check_refuse(me, "domain_size must be at least 2");
+  if (encoding != GM_ENC_COMPRESSED && encoding != GM_ENC_RAW) return check_refuse(me, "unknown encoding");
+  if (flags & ~(unsigned)(GM_DECODE_NO_SUBGROUP_CHECK | GM_PK_PRECOMPUTE | GM_PK_PRECOMPUTE_AUTO))
+    return check_refuse(me, "unknown flags");
+  const bool raw = encoding == GM_ENC_RAW;
+  const unsigned dflags = flags & GM_DECODE_NO_SUBGROUP_CHECK;
+  for (int m = 0; m < GM_G16_PK_MEMBERS; m++) points_decode_report_zero(&report->member[m], 0);
+  report->first_bad_member = -1;
+  // the file's layout: (report member, records, G2, has a length prefix) in writeTo's order
+  struct Part {
+    int member;
+    size_t n;
+    bool g2, slice;
+    uint64_t pos;  // first record byte
+  } parts[GM_G16_PK_MEMBERS] = {
+      {GM_G16_PK_G1_ALPHA, 1, false, false, 0}, {GM_G16_PK_G1_BETA, 1, false, false, 0},
+      {GM_G16_PK_G1_DELTA, 1, false, false, 0}, {GM_G16_PK_G1_A, meta->nbA, false, true, 0},
+      {GM_G16_PK_G1_B, meta->nbB, false, true, 0}, {GM_G16_PK_G1_Z, meta->domain_size - 1, false, true, 0},
+      {GM_G16_PK_G1_K, meta->nbK, false, true, 0}, {GM_G16_PK_G2_BETA, 1, true, false, 0},
+      {GM_G16_PK_G2_DELTA, 1, true, false, 0}, {GM_G16_PK_G2_B, meta->nbB, true, true, 0}};
+  uint64_t off = offset;
+  for (auto& p : parts) {
+    if (p.slice) {
+      uint8_t be[4];
+      if (int rc = read_at(fd, be, 4, off)) {
+        report->first_bad_member = p.member;
+        set_error(std::string(me) + ": member " + std::to_string(p.member) + ": the length prefix cannot be read (" +
+                  last_error() + ")");
+        return rc;
+      }
+      const uint64_t cnt = ((uint64_t)be[0] << 24) | ((uint64_t)be[1] << 16) | ((uint64_t)be[2] << 8) | be[3];
+      if (cnt != p.n) {
+        set_error(std::string(me) + ": member " + std::to_string(p.member) + " holds " + std::to_string(cnt) +
+                  " points, expected " + std::to_string(p.n));
+        report->first_bad_member = p.member;
+        return GM_ERR_INVALID;
+      }
+      off += 4;
+    }
+    p.pos = off;
+    off += (uint64_t)p.n * codec_record_bytes(curve, p.g2, raw);
+  }
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  const size_t chunk = ctx->points_check_chunk ? ctx->points_check_chunk : POINTS_CHECK_CHUNK;
+  size_t most = 1;  // records of the largest chunk, by the G1 record (the smallest)
+  for (const auto& p : parts) most = std::max(most, std::min(std::max<size_t>(chunk / codec_record_bytes(curve, p.g2, raw), 1), p.n));
+  IoRing ring;
+  if (int rc = ring.init(true, most * codec_record_bytes(curve, true, raw))) return rc;
+  Arena arena(ctx);
+  DevBuf res, gnark;  // the result words; one chunk of decoded points in gnark layout
+  if (int rc = res.alloc(arena, CD_RES_WORDS * sizeof(unsigned long long))) return rc;
+  if (int rc = gnark.alloc(arena, most * codec_point_bytes(curve, true))) return rc;
+  unsigned long long* r = res.as<unsigned long long>();
+  size_t slot = 0;
+  // Decodes part p chunk by chunk; each decoded chunk goes to `sink` (device
+  // pointer, first index, count) before the next one overwrites it.  GM_ERR_INVALID
+  // when a record fails (the report says which).
+  auto run_part = [&](const Part& p, const std::function<int(const void*, size_t, size_t)>& sink) -> int {
+    gm_points_decode_report* rep = &report->member[p.member];
+    points_decode_report_zero(rep, p.n);
+    const size_t rb = codec_record_bytes(curve, p.g2, raw);
+    const size_t per = std::max<size_t>(chunk / rb, 1);
+    int rc;
+    if ((rc = points_decode_reset(ctx, r))) return rc;
+    for (size_t i0 = 0; i0 < p.n; i0 += per, slot ^= 1) {
+      const size_t cnt = std::min(per, p.n - i0);
+      if ((rc = ring.acquire((int)slot))) return rc;
+      if ((rc = read_at(fd, ring.host[slot], cnt * rb, p.pos + i0 * rb))) {
+        report->first_bad_member = p.member;  // the file ends early: the chunk that could not be read
+        rep->first_bad = i0;
+        set_error(std::string(me) + ": member " + std::to_string(p.member) + ": records " + std::to_string(i0) +
+                  " to " + std::to_string(i0 + cnt - 1) + " cannot be read (" + last_error() + ")");
+        return rc;
+      }
+      GM_HIP(hipMemcpyAsync(ring.dev[slot], ring.host[slot], cnt * rb, hipMemcpyHostToDevice, ctx->stream));
+      if ((rc = points_decode_queue(ctx, curve, p.g2, raw, dflags, ring.dev[slot], cnt, i0, gnark.p, nullptr, r)))
+        return rc;
+      if ((rc = sink(gnark.p, i0, cnt))) return rc;
+      GM_HIP(hipEventRecord(ring.ev[slot], ctx->stream));
+    }
+    if ((rc = points_decode_read(ctx, r, p.n, rep))) return rc;
+    if (rep->first_bad != rep->n) {
+      report->first_bad_member = p.member;
+      set_error(std::string(me) + ": member " + std::to_string(p.member) + ", record " +
+                std::to_string(rep->first_bad) + " is refused (class " + std::to_string(rep->first_class) + ")");
+      return GM_ERR_INVALID;
+    }
+    return GM_OK;
+  };
+  // The members are decoded in the file's order, so that the first failing one is
+  // the first in the file: the single points before part `upto` that are not yet
+  // decoded go first (singles_out: three G1, two G2, the order of the report's members).
+  const size_t g1b = codec_point_bytes(curve, false), g2b = codec_point_bytes(curve, true);
+  char* singles = (char*)singles_out;
+  char* const single_at[5] = {singles, singles + g1b, singles + 2 * g1b, singles + 3 * g1b, singles + 3 * g1b + g2b};
+  int next_part = 0;  // parts[0, next_part) are decoded
+  auto singles_before = [&](int upto) -> int {
+    for (; next_part < upto; next_part++) {
+      const Part& p = parts[next_part];
+      if (p.slice) return check_refuse(me, "the key's arrays are not fetched in the file's order");
+      char* dst = single_at[p.member];
+      const size_t pb = p.g2 ? g2b : g1b;
+      const int rc = run_part(p, [&](const void* dev, size_t, size_t) -> int {
+        GM_HIP(hipMemcpyAsync(dst, dev, pb, hipMemcpyDeviceToHost, ctx->stream));
+        GM_HIP(hipStreamSynchronize(ctx->stream));
+        return GM_OK;
+      });
+      if (rc) return rc;
+    }
+    return GM_OK;
+  };
+  gm_g16_pk_host h = *meta;
+  h.g1_alpha = single_at[0];
+  h.g1_beta = single_at[1];
+  h.g1_delta = single_at[2];
+  h.g2_beta = single_at[3];
+  h.g2_delta = single_at[4];
+  Ranges rg = {0, meta->nbA, 0, meta->nbB, 0, meta->nbK, 0, meta->domain_size - 1, false};
+  const int part_of[5] = {3, 4, 5, 6, 9};  // PK_A, PK_B, PK_Z, PK_K, PK_B2 in `parts`
+  PointSource src = [&](int which, size_t count, bool g2, const MsmPrecomp* pre, void* dst) -> int {
+    const Part& p = parts[part_of[which]];
+    if (count != p.n || g2 != p.g2) return check_refuse(me, "the key asks for an array the file does not hold");
+    // pk_upload_ranges fetches A, B, Z, K, B2: the file's order, G2 beta and delta before G2.B
+    if (part_of[which] < next_part) return check_refuse(me, "the key's arrays are not fetched in the file's order");
+    int rc = singles_before(part_of[which]);
+    if (rc) return rc;
+    next_part = part_of[which] + 1;
+    const size_t ipb = internal_point_bytes(curve, g2);
+    rc = run_part(p, [&](const void* dev, size_t i0, size_t cnt) -> int {
+      return prepare_points_into(ctx, curve, g2, dev, cnt, pre, (char*)dst + i0 * ipb);
+    });
+    if (rc) return rc;
+    GM_HIP(hipStreamSynchronize(ctx->stream));
+    return GM_OK;
+  };
+  const int rc = pk_upload_ranges(ctx, curve, &h, flags & (GM_PK_PRECOMPUTE | GM_PK_PRECOMPUTE_AUTO), rg, out, &src);
+  if (rc) {
+    *out = nullptr;
+    return rc;
+  }
+  if (end_offset) *end_offset = off;
+  return GM_OK;
 }
 
 int gm_g16_pk_check(gm_ctx* ctx, int curve, const gm_g16_pk_host* pk, gm_g16_pk_report* out) {

@@ -1,0 +1,6 @@
+// Point codec, BLS12-377: the G1 and G2 instantiations of points_codec_impl.hpp.
+#include "points_codec_impl.hpp"
+
+namespace gm {
+GM_CD_INSTANTIATE(CurveBLS12377)
+}  // namespace gm

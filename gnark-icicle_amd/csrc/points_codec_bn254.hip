@@ -1,0 +1,6 @@
+// Point codec, BN254: the G1 and G2 instantiations of points_codec_impl.hpp.
+#include "points_codec_impl.hpp"
+
+namespace gm {
+GM_CD_INSTANTIATE(CurveBN254)
+}  // namespace gm

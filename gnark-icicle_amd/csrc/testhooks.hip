@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "curves.hpp"
+#include "field_sqrt.hpp"
 #include "msm.hpp"
 #include "pair_fp2.hpp"
 #include "runtime.hpp"
@@ -458,6 +459,30 @@ int gm_test_point_raw_op(gm_ctx* ctx, int curve, int g2, int op, int chain, cons
 }
 
 extern "C++" {
+// fe_sqrt (field_sqrt.hpp) on its own: gnark-form elements in, a root in gnark
+// form and the exists byte out
+template <class F>
+__global__ void k_fe_sqrt(const uint8_t* a, uint8_t* root, uint8_t* exists, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  F r;
+  const bool ok = fe_sqrt(ElemIO<F>::load(a, i), r);
+  ElemIO<F>::store(root, i, r);
+  exists[i] = ok ? 1 : 0;
+}
+template <class C>
+static int fe_sqrt_t(gm_ctx* ctx, int kind, const void* a, size_t n, void* root, void* exists) {
+  auto g = dim3(blocks_for(n, 64)), t = dim3(64);
+  if (kind == 1)
+    hipLaunchKernelGGL(k_fe_sqrt<typename C::G1F>, g, t, 0, ctx->stream, (const uint8_t*)a, (uint8_t*)root,
+                       (uint8_t*)exists, n);
+  else
+    hipLaunchKernelGGL(k_fe_sqrt<typename C::G2F>, g, t, 0, ctx->stream, (const uint8_t*)a, (uint8_t*)root,
+                       (uint8_t*)exists, n);
+  GM_HIP(hipGetLastError());
+  GM_HIP(hipStreamSynchronize(ctx->stream));
+  return GM_OK;
+}
 template <class C>
 static int field_op_t(gm_ctx* ctx, int kind, int op, const void* a, const void* b, void* out, size_t n) {
   auto g = dim3(blocks_for(n, 64)), t = dim3(64);
@@ -489,6 +514,15 @@ int gm_test_field_op(gm_ctx* ctx, int curve, int kind, int op, const void* a_dev
   GM_HIP(hipSetDevice(ctx->device));
   if (kind < 0 || kind > 2) return GM_ERR_INVALID;
   return GM_CURVE(curve, field_op_t<C>(ctx, kind, op, a_dev, b_dev, out_dev, n));
+}
+int gm_test_fe_sqrt(gm_ctx* ctx, int curve, int kind, const void* a_dev, size_t n, void* root_dev,
+                    uint8_t* exists_dev) {
+  if (int rc = check_curve(curve, CURVES_ALL, "gm_test_fe_sqrt")) return rc;
+  if (!ctx || kind < 1 || kind > 2 || (n && (!a_dev || !root_dev || !exists_dev))) return GM_ERR_INVALID;
+  if (n == 0) return GM_OK;
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  return GM_CURVE(curve, fe_sqrt_t<C>(ctx, kind, a_dev, n, root_dev, exists_dev));
 }
 int gm_test_point_op(gm_ctx* ctx, int curve, int g2, int op, const void* a_dev, const void* b_dev,
                      void* out_dev, size_t n) {

@@ -68,11 +68,12 @@ SYMBOLS = [
     "gm_set_g16_setup_column_cut", "gm_g16_setup_sizes", "gm_g16_setup", "gm_g16_pk_setup",
     "gm_points_check", "gm_points_check_host", "gm_set_points_check_chunk", "gm_g16_pk_check",
     "gm_g16_pk_check_dump",
+    "gm_points_decode", "gm_points_decode_host", "gm_points_encode", "gm_g16_pk_upload_encoded",
 ]
 # test-only library (include/gnark_mi355x_testhooks.h, libgnark_mi355x_testhooks.so)
 TEST_SYMBOLS = ["gm_test_field_op", "gm_test_point_op", "gm_test_stage_replay_chain",
                 "gm_test_msm_g2_keyless_plan", "gm_test_field_raw_op", "gm_test_point_raw_op",
-                "gm_test_msm_geometry", "gm_test_scan"]
+                "gm_test_msm_geometry", "gm_test_scan", "gm_test_fe_sqrt"]
 TESTHOOKS_PATH = os.path.join(os.path.dirname(LIB_PATH), "libgnark_mi355x_testhooks.so")
 
 
@@ -211,6 +212,33 @@ class _PointsReport(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+# point encodings (gm_points_decode*, gm_points_encode): the two further classes of a
+# record, the widths and the decode flag
+POINT_BAD_ENCODING, POINT_NO_ROOT = 4, 5
+ENC_COMPRESSED, ENC_RAW = 0, 1
+DECODE_NO_SUBGROUP_CHECK = 0x100
+
+
+class _PointsDecodeReport(ctypes.Structure):
+    """gm_points_decode_report (include/gnark_mi355x.h)."""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("n", "infinities", "not_reduced", "off_curve", "off_subgroup",
+                                               "bad_encoding", "no_root", "first_bad")] + [("first_class",
+                                                                                            ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class _G16PkDecodeReport(ctypes.Structure):
+    """gm_g16_pk_decode_report (include/gnark_mi355x.h)."""
+    _fields_ = [("member", _PointsDecodeReport * len(G16_PK_MEMBERS)), ("first_bad_member", ctypes.c_int32)]
+
+    def as_dict(self) -> dict:
+        out = {name: self.member[i].as_dict() for i, name in enumerate(G16_PK_MEMBERS)}
+        out["first_bad_member"] = None if self.first_bad_member < 0 else G16_PK_MEMBERS[self.first_bad_member]
+        return out
+
+
 class _G16PkReport(ctypes.Structure):
     _fields_ = [("member", _PointsReport * len(G16_PK_MEMBERS)), ("first_bad_member", ctypes.c_int32)]
 
@@ -221,6 +249,9 @@ class _G16PkReport(ctypes.Structure):
 
 
 TGEOM_MAX_LEVELS = 24
+# lanes per block of gm_test_fe_sqrt's kernel (csrc/testhooks.hip fe_sqrt_t): element i
+# runs in lane i % 64 of block i // 64, one wave per block
+FE_SQRT_HOOK_BLOCK = 64
 
 
 class _MsmGeom(ctypes.Structure):
@@ -256,6 +287,7 @@ def load_testhooks(path: str = None):
     T.gm_test_point_raw_op.argtypes = [vp, i, i, i, i, vp, vp, vp, vp, sz]
     T.gm_test_msm_geometry.argtypes = [i, i, sz, i, i, ctypes.POINTER(_MsmGeom)]
     T.gm_test_scan.argtypes = [vp, i, vp, sz, vp]
+    T.gm_test_fe_sqrt.argtypes = [vp, i, i, vp, sz, vp, vp]
     _testhooks = T
     return T
 
@@ -395,6 +427,12 @@ def load_library(path: str = LIB_PATH):
     L.gm_set_points_check_chunk.argtypes = [vp, sz]
     L.gm_g16_pk_check.argtypes = [vp, i, vp, ctypes.POINTER(_G16PkReport)]
     L.gm_g16_pk_check_dump.argtypes = [vp, i, vp, i, u64, ctypes.POINTER(_G16PkReport), ctypes.POINTER(u64)]
+    L.gm_points_decode.argtypes = [vp, i, i, i, ctypes.c_uint, vp, sz, vp, vp, ctypes.POINTER(_PointsDecodeReport)]
+    L.gm_points_decode_host.argtypes = [vp, i, i, i, ctypes.c_uint, vp, sz, vp, vp,
+                                        ctypes.POINTER(_PointsDecodeReport)]
+    L.gm_points_encode.argtypes = [vp, i, i, i, vp, sz, vp, ctypes.POINTER(u64)]
+    L.gm_g16_pk_upload_encoded.argtypes = [vp, i, vp, i, u64, i, ctypes.c_uint, vp,
+                                           ctypes.POINTER(_G16PkDecodeReport), ctypes.POINTER(u64), pvp]
     _lib = L
     return L
 
@@ -420,6 +458,11 @@ def curve_id(curve) -> int:
 
 def point_bytes(curve, g2: bool) -> int:
     return FP_BYTES[curve_id(curve)] * (4 if g2 else 2)
+
+
+def record_bytes(curve, g2: bool, encoding: int) -> int:
+    """Bytes of one gnark-crypto record of a point (ENC_COMPRESSED or ENC_RAW)."""
+    return FP_BYTES[curve_id(curve)] * (2 if g2 else 1) * (2 if encoding == ENC_RAW else 1)
 
 
 def jac_bytes(curve, g2: bool) -> int:
@@ -559,6 +602,71 @@ class Context:
     def set_points_check_chunk(self, nbytes: int):
         """Test knob: the chunk of the streamed point checks (0 = the default)."""
         _check(load_library().gm_set_points_check_chunk(self.handle, nbytes))
+
+    # ---- point encodings ---------------------------------------------------
+    def points_decode(self, curve, records: DeviceBuffer, n: int, g2: bool = False, encoding: int = ENC_COMPRESSED,
+                      flags: int = 0, status: bool = False):
+        """gm_points_decode over n device-resident records: (points, report), the
+        points as a new DeviceBuffer in gnark layout; with status=True also the
+        class byte of every record."""
+        rep = _PointsDecodeReport()
+        pts = self.malloc(max(n, 1) * point_bytes(curve, g2))
+        st = self.malloc(max(n, 1)) if status else None
+        try:
+            _check(load_library().gm_points_decode(self.handle, curve_id(curve), int(g2), encoding, flags,
+                                                   records.ptr, n, pts.ptr, st.ptr if st else None,
+                                                   ctypes.byref(rep)))
+            if st is None:
+                return pts, rep.as_dict()
+            return pts, rep.as_dict(), np.frombuffer(st.to_host(n), np.uint8)
+        except Exception:
+            pts.free()
+            raise
+        finally:
+            if st is not None:
+                st.free()
+
+    def points_decode_host(self, curve, records, g2: bool = False, encoding: int = ENC_COMPRESSED, flags: int = 0,
+                           points_dev: DeviceBuffer = None, to_host: bool = True):
+        """gm_points_decode_host: records in host memory, streamed in chunks.
+        Returns (the points as bytes, or None with to_host=False; the report)."""
+        a = _buf(records)
+        n = a.size // record_bytes(curve, g2, encoding)
+        out = np.zeros(n * point_bytes(curve, g2), np.uint8) if to_host else None
+        rep = _PointsDecodeReport()
+        _check(load_library().gm_points_decode_host(self.handle, curve_id(curve), int(g2), encoding, flags, _p(a), n,
+                                                    points_dev.ptr if points_dev else None,
+                                                    _p(out) if to_host else None, ctypes.byref(rep)))
+        return (out.tobytes() if to_host else None), rep.as_dict()
+
+    def points_encode(self, curve, points: DeviceBuffer, n: int, g2: bool = False, encoding: int = ENC_COMPRESSED):
+        """gm_points_encode: (the records as a new DeviceBuffer, the count of
+        points with a coordinate >= p, which are written as zero records)."""
+        enc = self.malloc(max(n, 1) * record_bytes(curve, g2, encoding))
+        bad = ctypes.c_uint64()
+        try:
+            _check(load_library().gm_points_encode(self.handle, curve_id(curve), int(g2), encoding, points.ptr, n,
+                                                   enc.ptr, ctypes.byref(bad)))
+        except Exception:
+            enc.free()
+            raise
+        return enc, int(bad.value)
+
+    def test_fe_sqrt(self, curve, elems, fp2: bool = False):
+        """gm_test_fe_sqrt (test-only library): gnark-form Fp or Fp2 elements ->
+        (roots in gnark form, exists bytes)."""
+        a = _buf(elems)
+        eb = FP_BYTES[curve_id(curve)] * (2 if fp2 else 1)
+        n = a.size // eb
+        src, root, ex = self.copy_to_device(a), self.malloc(max(a.size, 1)), self.malloc(max(n, 1))
+        try:
+            rc = load_testhooks().gm_test_fe_sqrt(self.handle, curve_id(curve), 2 if fp2 else 1, src.ptr, n, root.ptr,
+                                                  ex.ptr)
+            _check(rc)
+            return root.to_host(n * eb), np.frombuffer(ex.to_host(n), np.uint8)
+        finally:
+            for b in (src, root, ex):
+                b.free()
 
     def g16_pk_check(self, curve, pk: dict, domain_size: int, nb_wires: int, nb_public: int) -> dict:
         """gm_g16_pk_check: one report per member of the key ProvingKey would upload."""
@@ -1195,6 +1303,48 @@ class ProvingKey:
         self.handle = handle
         self.n, self.nb_wires, self.nb_public = domain_size, nb_wires, nb_public
         self.shard = (rank, world)
+
+    @classmethod
+    def from_encoded(cls, ctx: Context, curve, path: str, offset: int, meta: dict, domain_size: int, nb_wires: int,
+                     nb_public: int, encoding: int = ENC_COMPRESSED, flags: int = 0, precompute: bool = False):
+        """Streams the points of a gnark WriteTo (ENC_COMPRESSED) or WriteRawTo
+        (ENC_RAW) key file from byte `offset` (where G1.Alpha begins) through the
+        device decoder into a resident key (gm_g16_pk_upload_encoded).  `meta` holds
+        infA, infB, an optional k_wires and counts = (nbA, nbB, nbK).  Returns
+        (key, end_offset, report, singles): singles are the five decoded single
+        points in gnark layout.  A refused file raises GmError with the report as
+        its `report` attribute."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self.curve = curve_id(curve)
+        g1b, g2b = point_bytes(curve, False), point_bytes(curve, True)
+        stub = dict(meta)
+        for k, pb in (("g1_alpha", g1b), ("g1_beta", g1b), ("g1_delta", g1b), ("g2_beta", g2b), ("g2_delta", g2b),
+                      ("g1_A", g1b), ("g1_B", g1b), ("g1_Z", g1b), ("g1_K", g1b), ("g2_B", g2b)):
+            stub[k] = np.zeros(pb, np.uint8)
+        counts = stub.pop("counts")
+        h, arrs = _pk_host_struct(curve, stub, domain_size, nb_wires, nb_public)
+        h.nbA, h.nbB = counts[0], counts[1]
+        if not ("k_wires" in meta and meta["k_wires"] is not None):
+            h.nbK = counts[2]
+        self._keep, self._h = arrs, h
+        handle, end, rep = ctypes.c_void_p(), ctypes.c_uint64(), _G16PkDecodeReport()
+        singles = np.zeros(3 * g1b + 2 * g2b, np.uint8)
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            rc = load_library().gm_g16_pk_upload_encoded(ctx.handle, self.curve, ctypes.byref(h), fd, offset, encoding,
+                                                         flags | cls._flags(precompute), _p(singles),
+                                                         ctypes.byref(rep), ctypes.byref(end), ctypes.byref(handle))
+        finally:
+            os.close(fd)
+        if rc != 0:
+            err = GmError(f"gnark_mi355x error {rc}: {load_library().gm_last_error().decode()}")
+            err.rc, err.report, err.handle = rc, rep.as_dict(), handle.value
+            raise err
+        self.handle = handle
+        self.n, self.nb_wires, self.nb_public = domain_size, nb_wires, nb_public
+        self.shard = (0, 1)
+        return self, end.value, rep.as_dict(), singles.tobytes()
 
     @classmethod
     def from_dump(cls, ctx: Context, curve, path: str, offset: int, meta: dict, domain_size: int, nb_wires: int,

@@ -46,7 +46,8 @@ typedef enum {
  * upload and prover (gm_g16_pk_upload[_ex], gm_g16_prove[_device], gm_g16_finish,
  * gm_g16_partial_bytes) and the point validation of what those uploads take
  * (gm_points_check, gm_points_check_host, gm_g16_pk_check; gm_g16_pk_check_dump
- * stands with the dump loader below).  Every other entry that takes a curve --
+ * stands with the dump loader below) and the point codec (gm_points_decode,
+ * gm_points_decode_host, gm_points_encode).  Every other entry that takes a curve --
  * the PLONK calls
  * and gm_kzg_srs_lagrange, gm_r1cs_upload and what needs it (gm_g16_prove_r1cs,
  * gm_g16_setup*, gm_g16_pk_setup), gm_batch_mul_fixed / gm_batch_mul_base, the
@@ -999,6 +1000,106 @@ int gm_g16_pk_check(gm_ctx* ctx, int curve, const gm_g16_pk_host* pk, gm_g16_pk_
  * file is only read; no key is created. */
 int gm_g16_pk_check_dump(gm_ctx* ctx, int curve, const gm_g16_pk_host* meta, int fd, uint64_t offset,
                          gm_g16_pk_report* out, uint64_t* end_offset);
+
+/* ---- point encodings: gnark-crypto's compressed and raw records on the device
+ * What G1Affine / G2Affine.Bytes, RawBytes and the Encoder behind
+ * ProvingKey.WriteTo / WriteRawTo (backend/groth16/bn254/marshal.go:239-311) and
+ * kzg.SRS.WriteTo write, decoded and encoded one lane per record (DESIGN.md
+ * section 3.10).  A coordinate is 8 * fp_limbs bytes, big-endian, canonical (not
+ * Montgomery).  G1: X (GM_ENC_COMPRESSED) or X || Y (GM_ENC_RAW); G2: X.A1 || X.A0
+ * or X.A1 || X.A0 || Y.A1 || Y.A0.  The flag is the top bits of the record's
+ * first byte:
+ *   BN254 (two bits)        00 raw; 10 / 11 compressed, y the smaller / larger of
+ *                           {y, -y}; 01 compressed infinity; the raw infinity is
+ *                           the all-zero record
+ *   BLS12-377 / -381 (three bits; BLS12-381: the ZCash encoding)
+ *                           000 raw; 010 raw infinity; 100 / 101 compressed, smaller /
+ *                           larger; 110 compressed infinity; 001, 011, 111 invalid
+ * "Larger": the canonical value is > (p - 1) / 2; in Fp2 the rule is applied to A1,
+ * to A0 when A1 = 0.  An infinity record is zero outside its flag; the all-zero
+ * raw record is read as the infinity on every curve.  One call takes one width:
+ * a record whose flag belongs to the other width is refused.  The array passed
+ * has no length prefix (the Encoder's big-endian u32 count is the caller's).
+ *
+ * Decoding classes each record, the first class that applies:
+ *   GM_POINT_BAD_ENCODING  an invalid flag, a flag of the other width, an
+ *                          infinity record with other bits set
+ *   GM_POINT_NOT_REDUCED   a coordinate component >= p once the flag is cleared
+ *   GM_POINT_NO_ROOT       compressed: x^3 + b has no square root
+ *   GM_POINT_OFF_CURVE     raw: y^2 != x^3 + b
+ *   GM_POINT_OFF_SUBGROUP  [r]P != infinity
+ * GM_DECODE_NO_SUBGROUP_CHECK (gnark's NoSubgroupChecks) skips the last two.  A
+ * compressed point with y = 0 is accepted under either flag.  A refused record
+ * and an infinity are stored as (0, 0).  The entries return GM_OK when the
+ * decode ran, whatever it found: the report carries the verdict (first_bad = n
+ * if none).  n = 0 gives a zero report.  GM_ERR_INVALID before any launch: a
+ * NULL argument, an unknown encoding or flag, g2 outside {0, 1}, a device
+ * pointer that is not 16-byte aligned, overlapping input and output, an unknown
+ * curve id.  Curve ids 0, 1 and 2. */
+enum { GM_POINT_BAD_ENCODING = 4, GM_POINT_NO_ROOT = 5 };
+#define GM_ENC_COMPRESSED 0
+#define GM_ENC_RAW 1
+/* a bit of its own beside GM_PK_PRECOMPUTE[_AUTO]: the key loader takes both */
+#define GM_DECODE_NO_SUBGROUP_CHECK 0x100u
+typedef struct {
+  uint64_t n, infinities, not_reduced, off_curve, off_subgroup, bad_encoding, no_root, first_bad /* n if none */;
+  uint32_t first_class;
+} gm_points_decode_report;
+/* enc_dev: n records on the device; points_dev receives n gnark affine points
+ * (the layout gm_copy_points_to_device leaves there); status_dev: NULL, or n
+ * bytes that receive each record's class. */
+int gm_points_decode(gm_ctx* ctx, int curve, int g2, int encoding, unsigned flags, const void* enc_dev, size_t n,
+                     void* points_dev, uint8_t* status_dev /* NULL or n bytes */, gm_points_decode_report* out);
+/* The same over records in host memory, streamed through the pinned chunk ring of
+ * the dump loader in the chunks gm_set_points_check_chunk sets (a chunk holds at
+ * least one record), so any n works.  The points go to points_dev (device, n
+ * points), to points_host (host, n points), or to both; at least one is given. */
+int gm_points_decode_host(gm_ctx* ctx, int curve, int g2, int encoding, unsigned flags, const void* enc_host,
+                          size_t n, void* points_dev /* or NULL */, void* points_host /* or NULL */,
+                          gm_points_decode_report* out);
+/* The reverse: n gnark affine points on the device to n records at enc_dev.
+ * (0, 0) becomes the infinity record.  A point with a coordinate component >= p
+ * is counted in *not_reduced and written as a zero record; nothing else is
+ * checked. */
+int gm_points_encode(gm_ctx* ctx, int curve, int g2, int encoding, const void* points_dev, size_t n, void* enc_dev,
+                     uint64_t* not_reduced);
+/* A Groth16 proving key from the stream ProvingKey.WriteTo (GM_ENC_COMPRESSED) or
+ * WriteRawTo (GM_ENC_RAW) writes (backend/groth16/bn254/marshal.go:239-311), as
+ * gm_g16_pk_upload_dump takes a WriteDump file.  `offset` is the byte after
+ * Domain.WriteTo, where G1.Alpha begins.  The members are read in writeTo's
+ * order: G1 alpha, beta, delta (single records), G1 A, B, Z, K (slices: a
+ * big-endian u32 count, then the records), G2 beta, delta (single records), G2 B
+ * (slice).  Slice lengths are checked against `meta` (nbA, nbB, domain_size - 1,
+ * nbK, nbB), whose infA / infB / k_wires are used as gm_g16_pk_upload uses them;
+ * its point pointers are ignored.  Every slice is streamed through the pinned
+ * chunk ring (chunks as gm_set_points_check_chunk sets them), decoded on the
+ * device and converted into the key's layout; no decoded array is kept.  The
+ * five decoded single points go to singles_out on the host in gnark layout: three
+ * G1 points, then two G2 points.  `flags` takes GM_DECODE_NO_SUBGROUP_CHECK and
+ * GM_PK_PRECOMPUTE[_AUTO].  The report has one gm_points_decode_report per member
+ * in the order of GM_G16_PK_G1_ALPHA... (the enum's order, not the file's).  All
+ * four-byte slice lengths are read and compared first; then the members are
+ * decoded in the file's order, and decoding stops at the first member with a
+ * failing record: no key is created, *pk is NULL, the call returns
+ * GM_ERR_INVALID, first_bad_member is that member, the first in the file's order
+ * (a bad G1.A is named before a bad G2 beta), and its first_bad / first_class say
+ * where; the members behind it in the file report n = 0.  The failing member
+ * itself is decoded to its end before its report is read (one read per slice
+ * keeps the copies and kernels overlapped), so an early bad record of a long
+ * slice costs the whole slice.  A slice whose length differs from `meta`'s is
+ * refused with first_bad_member naming it.  A file that ends early is refused the
+ * same way: first_bad_member names the member whose bytes are missing, first_bad
+ * is the first record of the chunk that could not be read (first_class stays
+ * GM_POINT_OK), and gm_last_error names the member and the records.  *end_offset (may be NULL) is the first byte
+ * after G2.B, where nbWires follows.  The file position of fd is not used or
+ * moved.  Curve ids 0 and 1 (GM_ERR_UNSUPPORTED for 2, like gm_g16_pk_upload_dump). */
+typedef struct {
+  gm_points_decode_report member[GM_G16_PK_MEMBERS];
+  int32_t first_bad_member; /* the first member with a failing record, -1 if none */
+} gm_g16_pk_decode_report;
+int gm_g16_pk_upload_encoded(gm_ctx* ctx, int curve, const gm_g16_pk_host* meta, int fd, uint64_t offset,
+                             int encoding, unsigned flags, void* singles_out, gm_g16_pk_decode_report* report,
+                             uint64_t* end_offset, gm_g16_pk** pk);
 
 /* ---- staged prover inputs --------------------------
  * The R1CS solver (constraint/bn254/solver.go:426-532) makes a, b, c final

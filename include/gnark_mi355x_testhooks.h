@@ -20,6 +20,13 @@ int gm_test_field_op(gm_ctx* ctx, int curve, int kind, int op, const void* a_dev
 int gm_test_point_op(gm_ctx* ctx, int curve, int g2, int op, const void* a_dev,
                      const void* b_dev, void* out_dev, size_t n);
 
+/* fe_sqrt (csrc/field_sqrt.hpp) on its own: n elements in gnark form at a_dev,
+ * kind 1 = Fp, 2 = Fp2 ({A0, A1}).  root_dev receives n elements in gnark form,
+ * exists_dev n bytes: 1 and a square root where the element is a square, else 0
+ * (the element at root_dev is then unspecified). */
+int gm_test_fe_sqrt(gm_ctx* ctx, int curve, int kind, const void* a_dev, size_t n, void* root_dev,
+                    uint8_t* exists_dev);
+
 /* Raw-limb hooks for the lazily reduced layer (field.hpp "Lazily reduced
  * arithmetic", curve.hpp, pair_fp2.hpp).  Elements cross the boundary as the
  * internal radix-2^29 limbs: N little-endian u32 per element (N = 9, or 14 for
