@@ -44,6 +44,7 @@ namespace {
 
 using BnFp2 = Fe2<BnFp, -1>;
 using BlsFp2 = Fe2<BlsFp, -5>;
+using Bls381Fp2 = Fe2<Bls381Fp, -1>;
 
 template <class FR, class FP, class FP2, int NBITS, int TWO_ADICITY, uint64_t COSET_GEN,
           int CURVE_ID>
@@ -60,6 +61,7 @@ struct Curve {
 
 using BN = Curve<BnFr, BnFp, BnFp2, 254, 28, 5, 0>;
 using BLS = Curve<BlsFr, BlsFp, BlsFp2, 253, 47, 22, 1>;
+using BLS381 = Curve<Bls381Fr, Bls381Fp, Bls381Fp2, 255, 32, 7, 2>;
 
 // ---------------------------------------------------------------------------
 // helpers
@@ -765,8 +767,11 @@ static const uint64_t G_BN_G1[] = O_BN254_G1_GEN;
 static const uint64_t G_BN_G2[] = O_BN254_G2_GEN;
 static const uint64_t G_BLS_G1[] = O_BLS12377_G1_GEN;
 static const uint64_t G_BLS_G2[] = O_BLS12377_G2_GEN;
+static const uint64_t G_BLS381_G1[] = O_BLS12381_G1_GEN;
+static const uint64_t G_BLS381_G2[] = O_BLS12381_G2_GEN;
 const uint8_t* curve_gen(int id, int g2) {
   if (id == 0) return (const uint8_t*)(g2 ? G_BN_G2 : G_BN_G1);
+  if (id == 2) return (const uint8_t*)(g2 ? G_BLS381_G2 : G_BLS381_G1);
   return (const uint8_t*)(g2 ? G_BLS_G2 : G_BLS_G1);
 }
 
@@ -783,12 +788,16 @@ int o_msm(int curve, int g2, const uint8_t* scalars, const uint8_t* points, size
   if (curve == 1)
     return g2 ? msm_impl<BLS, BlsFp2>(scalars, points, n, nthreads, naive, out_affine)
               : msm_impl<BLS, Fe<BlsFp>>(scalars, points, n, nthreads, naive, out_affine);
+  if (curve == 2)
+    return g2 ? msm_impl<BLS381, Bls381Fp2>(scalars, points, n, nthreads, naive, out_affine)
+              : msm_impl<BLS381, Fe<Bls381Fp>>(scalars, points, n, nthreads, naive, out_affine);
   return -1;
 }
 
 int o_fft(int curve, uint8_t* data, size_t n, int inverse, int dit, int coset, int nthreads) {
   if (curve == 0) return fft_impl<BN>(data, n, inverse, dit, coset, nthreads);
   if (curve == 1) return fft_impl<BLS>(data, n, inverse, dit, coset, nthreads);
+  if (curve == 2) return fft_impl<BLS381>(data, n, inverse, dit, coset, nthreads);
   return -1;
 }
 
@@ -796,6 +805,7 @@ int o_compute_h(int curve, const uint8_t* a, const uint8_t* b, const uint8_t* c,
                 size_t n, int nthreads, uint8_t* h_out) {
   if (curve == 0) return compute_h_impl<BN>(a, b, c, len, n, nthreads, h_out);
   if (curve == 1) return compute_h_impl<BLS>(a, b, c, len, n, nthreads, h_out);
+  if (curve == 2) return compute_h_impl<BLS381>(a, b, c, len, n, nthreads, h_out);
   return -1;
 }
 
@@ -823,6 +833,20 @@ int o_batch_mul_base(int curve, int g2, const uint8_t* base, const uint8_t* scal
       memcpy(&b, base, sizeof(b));
       batch_mul_base<BLS, Fe<BlsFp>>(b, scalars, n, nthreads,
                                      reinterpret_cast<Aff<Fe<BlsFp>>*>(out));
+    }
+    return 0;
+  }
+  if (curve == 2) {
+    if (g2) {
+      Aff<Bls381Fp2> b;
+      memcpy(&b, base, sizeof(b));
+      batch_mul_base<BLS381, Bls381Fp2>(b, scalars, n, nthreads,
+                                        reinterpret_cast<Aff<Bls381Fp2>*>(out));
+    } else {
+      Aff<Fe<Bls381Fp>> b;
+      memcpy(&b, base, sizeof(b));
+      batch_mul_base<BLS381, Fe<Bls381Fp>>(b, scalars, n, nthreads,
+                                           reinterpret_cast<Aff<Fe<Bls381Fp>>*>(out));
     }
     return 0;
   }
@@ -884,6 +908,7 @@ int o_g16_setup(int curve, size_t nc, size_t nb_wires, size_t nb_public, const u
   };
   if (curve == 0) return run(BN{});
   if (curve == 1) return run(BLS{});
+  if (curve == 2) return run(BLS381{});
   return -1;
 }
 
@@ -915,6 +940,7 @@ int o_g16_prove(int curve, const size_t* sizes, uint8_t* const* g1, uint8_t* con
   };
   if (curve == 0) return run(BN{});
   if (curve == 1) return run(BLS{});
+  if (curve == 2) return run(BLS381{});
   return -1;
 }
 
@@ -936,6 +962,7 @@ int o_g16_check_mask(int curve, size_t nc, size_t nb_wires, size_t nb_public, co
   };
   if (curve == 0) return run(BN{});
   if (curve == 1) return run(BLS{});
+  if (curve == 2) return run(BLS381{});
   return -1;
 }
 
@@ -957,6 +984,7 @@ int o_g16_check(int curve, size_t nc, size_t nb_wires, size_t nb_public, const u
   };
   if (curve == 0) return run(BN{});
   if (curve == 1) return run(BLS{});
+  if (curve == 2) return run(BLS381{});
   return -1;
 }
 

@@ -28,6 +28,8 @@ ORC_FIELD(BnFp, BN254_FP, 4)
 ORC_FIELD(BnFr, BN254_FR, 4)
 ORC_FIELD(BlsFp, BLS12377_FP, 6)
 ORC_FIELD(BlsFr, BLS12377_FR, 4)
+ORC_FIELD(Bls381Fp, BLS12381_FP, 6)
+ORC_FIELD(Bls381Fr, BLS12381_FR, 4)
 
 template <class D>
 struct Fe {

@@ -14,8 +14,8 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "_build", "liboracle.so")
 
-CURVE_ID = {"bn254": 0, "bls12377": 1}
-FP_BYTES = {"bn254": 32, "bls12377": 48}
+CURVE_ID = {"bn254": 0, "bls12377": 1, "bls12381": 2}
+FP_BYTES = {"bn254": 32, "bls12377": 48, "bls12381": 48}
 FR_BYTES = 32
 
 _lib = None

@@ -1,7 +1,8 @@
-"""BLS12-381 for the frozen Python oracle: a pyref.CurveParams built from the
-curve's published constants, so that pyref's Group, fft, compute_h, g16_setup,
-g16_prove and the encoders serve as the reference of curve id 2 without a
-change under oracle/.  (The C++ oracle does not know the curve.)"""
+"""BLS12-381 (curve id 2) for the tests: the curve's published constants, the
+pyref.CurveParams the oracles hold for it (pyref.CURVES["bls12381"], checked
+against those constants here) and the small encoders and circuit builders the
+test_bls12381_* files share.  Their expectations come from pyref and from
+points of known discrete log, independently of the C++ oracle."""
 import os
 import sys
 
@@ -20,25 +21,18 @@ CURVE_ID = 2
 FP_BYTES = 48
 FR_BITS = 255
 
-BLS12_381 = pyref.CurveParams(
-    name="bls12381",
-    p=P,
-    r=R,
-    fp_limbs=6,
-    fr_limbs=4,
-    b=4,
-    beta=P - 1,                       # Fp2 = Fp[u]/(u^2 + 1)
-    b2=(4, 4),                        # twist y^2 = x^3 + 4 (1 + u)
-    g1=(0x17f1d3a73197d7942695638c4fa9ac0fc3688c4f9774b905a14e3a3f171bac586c55e83ff97a1aeffb3af00adb22c6bb,
-        0x08b3f481e3aaa0f1a09e30ed741d8ae4fcf5e095d5d00af600db18cb2c04b3edd03cc744a2888ae40caa232946c5e7e1),
-    g2=((0x024aa2b2f08f0a91260805272dc51051c6e47ad4fa403b02b4510b647ae3d1770bac0326a805bbefd48056c8c121bdb8,
-         0x13e02b6052719f607dacd3a088274f65596bd0d09920b61ab5da61bbdc7f5049334cf11213945d57e5ac7d055d042b7e),
-        (0x0ce5d527727d6e118cc9cdc6da2e351aadfd9baa8cbdd3a76d429a695160d12c923ac9cc3baca289e193548608b82801,
-         0x0606c4a02ea734cc32acd2b02bc28b99cb3e287e85a763af267492ab572e99ab3f370d275cec1da1aaa9075ff05f79be)),
-    coset_gen=COSET_GEN,
-    omega_max=OMEGA_MAX,
-    two_adicity=TWO_ADICITY,
-)
+# the published generators (canonical coordinates); the oracles' own copies are
+# held equal to these by tests/test_oracle.py
+G1_GEN = (0x17f1d3a73197d7942695638c4fa9ac0fc3688c4f9774b905a14e3a3f171bac586c55e83ff97a1aeffb3af00adb22c6bb,
+          0x08b3f481e3aaa0f1a09e30ed741d8ae4fcf5e095d5d00af600db18cb2c04b3edd03cc744a2888ae40caa232946c5e7e1)
+G2_GEN = ((0x024aa2b2f08f0a91260805272dc51051c6e47ad4fa403b02b4510b647ae3d1770bac0326a805bbefd48056c8c121bdb8,
+           0x13e02b6052719f607dacd3a088274f65596bd0d09920b61ab5da61bbdc7f5049334cf11213945d57e5ac7d055d042b7e),
+          (0x0ce5d527727d6e118cc9cdc6da2e351aadfd9baa8cbdd3a76d429a695160d12c923ac9cc3baca289e193548608b82801,
+           0x0606c4a02ea734cc32acd2b02bc28b99cb3e287e85a763af267492ab572e99ab3f370d275cec1da1aaa9075ff05f79be))
+
+BLS12_381 = pyref.CURVES["bls12381"]
+assert (BLS12_381.p, BLS12_381.r, BLS12_381.g1, BLS12_381.g2) == (P, R, G1_GEN, G2_GEN)
+assert (BLS12_381.coset_gen, BLS12_381.omega_max, BLS12_381.two_adicity) == (COSET_GEN, OMEGA_MAX, TWO_ADICITY)
 
 C = BLS12_381
 NAME = "bls12381"

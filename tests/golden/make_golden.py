@@ -86,9 +86,10 @@ def g16_case(cname, circ, W, toxic, r_, s_):
 
 def main():
     out = {}
-    for cname, g2, n in [("bn254", False, 64), ("bn254", True, 32), ("bls12377", False, 32), ("bls12377", True, 16)]:
+    for cname, g2, n in [("bn254", False, 64), ("bn254", True, 32), ("bls12377", False, 32), ("bls12377", True, 16),
+                          ("bls12381", False, 32), ("bls12381", True, 16)]:
         out["msm_%s_%s" % (cname, "g2" if g2 else "g1")] = msm_case(cname, g2, n, 4242 + n + g2)
-    for cname in ("bn254", "bls12377"):
+    for cname in ("bn254", "bls12377", "bls12381"):
         out["ntt_%s" % cname] = ntt_case(cname, 16, 99)
         r1, W = R.cubic_circuit(cname)
         out["h_cubic_%s" % cname] = h_case(cname, r1, W)
@@ -99,6 +100,8 @@ def main():
     out["groth16_cubic_bn254"] = g16_case("bn254", r1, W, toxic, 0x1234567, 0x7654321)
     r1, W = R.cubic_circuit("bls12377")
     out["groth16_cubic_bls12377"] = g16_case("bls12377", r1, W, toxic, 0x1234567, 0x7654321)
+    r1, W = R.cubic_circuit("bls12381")
+    out["groth16_cubic_bls12381"] = g16_case("bls12381", r1, W, toxic, 0x1234567, 0x7654321)
     for k, v in out.items():
         with open(os.path.join(HERE, k + ".json"), "w") as f:
             json.dump(v, f, indent=1)

@@ -36,7 +36,7 @@ def _prove_both(gm_ctx, oracle, cname, r1, W, rr, ss, precompute=False):
     return exp, got, ok
 
 
-@pytest.mark.parametrize("cname", ["bn254", "bls12377"])
+@pytest.mark.parametrize("cname", ["bn254", "bls12377", "bls12381"])
 def test_groth16_cubic(gm_ctx, oracle, cname):
     """examples/cubic (BASELINE config 1 circuit) -- n = 4."""
     r1, W = R.cubic_circuit(cname)
@@ -46,7 +46,7 @@ def test_groth16_cubic(gm_ctx, oracle, cname):
 
 
 @pytest.mark.parametrize("cname,k", [("bn254", 15), ("bn254", 1023), ("bn254", 4000),
-                                     ("bls12377", 511)])
+                                     ("bls12377", 511), ("bls12381", 511), ("bls12381", 4000)])
 def test_groth16_squaring_chain(gm_ctx, oracle, cname, k):
     """refCircuit of backend/groth16/groth16_test.go:120-156 with k squarings."""
     r1, W = R.squaring_chain(k, cname, x=2)
@@ -55,7 +55,7 @@ def test_groth16_squaring_chain(gm_ctx, oracle, cname, k):
     assert ok == 7
 
 
-@pytest.mark.parametrize("cname,k", [("bn254", 15), ("bn254", 4000), ("bls12377", 511)])
+@pytest.mark.parametrize("cname,k", [("bn254", 15), ("bn254", 4000), ("bls12377", 511), ("bls12381", 511)])
 def test_groth16_precomputed_pk(gm_ctx, oracle, cname, k):
     """GM_PK_PRECOMPUTE (fixed-base window copies of every pk array): the proof
     is byte-identical to the CPU restatement."""
@@ -80,9 +80,16 @@ def test_groth16_k_wire_filter(gm_ctx, oracle):
     given by the k_wires index map of the device pk.  Expected: the oracle prover
     on the full pk with the removed wires' K points set to infinity (so they
     contribute nothing)."""
+    _k_wire_filter(gm_ctx, oracle, "bn254")
+
+
+def test_groth16_k_wire_filter_bls12381(gm_ctx, oracle):
+    _k_wire_filter(gm_ctx, oracle, "bls12381")
+
+
+def _k_wire_filter(gm_ctx, oracle, cname):
     import numpy as np
     import gnark_mi355x as gm
-    cname = "bn254"
     c = pyref.CURVES[cname]
     r1, W = R.squaring_chain(200, cname, x=3)
     tox = R.encode_vec(cname, [t % c.r for t in TOXIC])
@@ -206,7 +213,7 @@ def test_groth16_multi_forced_peer_copies(gm_ctx, oracle, monkeypatch, cname, pr
 
 
 @pytest.mark.parametrize("cname,ncommit,precompute", [("bn254", 1, False), ("bn254", 2, True),
-                                                      ("bls12377", 2, False)])
+                                                      ("bls12377", 2, False), ("bls12381", 2, False)])
 def test_groth16_bsb22_commitments(gm_ctx, oracle, cname, ncommit, precompute):
     """A circuit with one / two BSB22 commitments (prove.go:82-139) at n = 2^13:
     the oracle solves it through the overridden commitment hint, proves and is
@@ -272,8 +279,17 @@ def test_groth16_shared_wire_plan_on_off(gm_ctx, oracle, monkeypatch, precompute
     A, B and K through wire maps (wires without a point are skipped entries);
     'copy' (w_{j+1} = w_j * ONE: B holds one point) shares A and K only and B /
     B2 keep their own plan."""
+    _shared_wire_plan_on_off(gm_ctx, oracle, monkeypatch, "bn254", precompute, shape)
+
+
+@pytest.mark.parametrize("shape", ["chain", "copy"])
+def test_groth16_shared_wire_plan_on_off_bls12381(gm_ctx, oracle, monkeypatch, shape):
+    """Both shapes on a BLS12-381 key of 3003 wires, plain arrays."""
+    _shared_wire_plan_on_off(gm_ctx, oracle, monkeypatch, "bls12381", False, shape)
+
+
+def _shared_wire_plan_on_off(gm_ctx, oracle, monkeypatch, cname, precompute, shape):
     import gnark_mi355x as gm
-    cname = "bn254"
     c = pyref.CURVES[cname]
     if shape == "chain":
         r1, W = R.squaring_chain(3000, cname, x=5)
@@ -331,9 +347,17 @@ def test_groth16_second_msm_stream_with_async_msm_pending(gm_ctx, oracle, monkey
     stream): host-input and device-input proofs equal the oracle's, also while a
     gm_msm_async MSM is pending on the same context (its slot stream is not the
     prove's), and that MSM's result is right."""
+    _second_msm_stream(gm_ctx, oracle, monkeypatch, "bn254", precompute)
+
+
+def test_groth16_second_msm_stream_with_async_msm_pending_bls12381(gm_ctx, oracle, monkeypatch):
+    _second_msm_stream(gm_ctx, oracle, monkeypatch, "bls12381", False)
+
+
+def _second_msm_stream(gm_ctx, oracle, monkeypatch, cname, precompute):
+    import device_points
     import gnark_mi355x as gm
     monkeypatch.setenv("GM_G16_MSM_STREAMS", "1")
-    cname = "bn254"
     c = pyref.CURVES[cname]
     r1, W = R.squaring_chain(3000, cname, x=6)
     tox = R.encode_vec(cname, [t % c.r for t in TOXIC])
@@ -345,7 +369,7 @@ def test_groth16_second_msm_stream_with_async_msm_pending(gm_ctx, oracle, monkey
     n = 1 << 16
     S = gm_ctx.random_scalars(cname, n, seed=0x91)
     K = gm_ctx.random_scalars(cname, n, seed=0x92)
-    P = gm_ctx.batch_mul_base(cname, False, gm.generator(cname), K, n)
+    P = device_points.batch_mul_generator(gm_ctx, cname, False, K, n)
     msm_exp = oracle.msm(cname, False, S.to_host(), P.to_host())
     dpk = gm.ProvingKey(gm_ctx, cname, pk, r1.domain_size, r1.nb_wires, r1.nb_public, precompute=precompute)
     try:

@@ -21,7 +21,7 @@ import pyref
 
 pytestmark = pytest.mark.gpu
 
-CURVE_NAMES = ("bls12377", "bn254")
+CURVE_NAMES = ("bls12377", "bn254", "bls12381")
 LENGTHS = [1, 2, 3, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049, 4097, (1 << 16) + 3,
            (1 << 18) + 3, (1 << 19) + 3]
 KINDS = ("random", "all_r_minus_1", "mostly_zero", "multiple_of_x_minus_z")
@@ -37,7 +37,7 @@ def _bytes(vals):
 
 def _random_mont(m, seed):
     """m field elements as the integers of their Montgomery words: any value
-    below r is one; 2^252 < r for both scalar fields."""
+    below r is one; 2^252 < r for all three scalar fields."""
     a = np.random.RandomState(seed).randint(0, 256, size=(m, 32), dtype=np.uint8)
     a[:, 31] &= 0x0F
     return _ints(a.tobytes())
@@ -220,7 +220,8 @@ def _srs(oracle, gm, cname, size, tau):
     return oracle.batch_mul_base(cname, False, gm.generator(cname), powers)
 
 
-@pytest.mark.parametrize("cname,logn", [("bls12377", 6), ("bls12377", 10), ("bn254", 6)])
+@pytest.mark.parametrize("cname,logn", [("bls12377", 6), ("bls12377", 10), ("bn254", 6),
+                                        ("bls12381", 6), ("bls12381", 10)])
 def test_kzg_open_and_batch_open(gm_ctx, oracle, cname, logn):
     import gnark_mi355x as gm
     c = pyref.CURVES[cname]

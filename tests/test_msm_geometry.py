@@ -2,7 +2,7 @@
 gm_test_msm_geometry calls the functions the driver calls (msm.hpp
 msm_plan_geom, msm_seg_geom, msm_tree_geom).  Checked here: the class table of
 every curve, group, layout and window width; that the GPU sweep
-(test_msm_windows_gpu.CASES) holds every class but the four the 16 GiB cap
+(test_msm_windows_gpu.CASES) holds every class but the seven the 16 GiB cap
 leaves out; that every default choice of window lies inside the sweep; and,
 with a Python restatement of the signed-digit recoding, that the sweep's
 structured scalars reach the edge buckets of every window."""
@@ -13,9 +13,12 @@ import pyref
 import test_msm_windows_gpu as sweep
 
 ALL = [(cn, g2, lay, c) for cn, g2 in sweep.GROUPS for lay in sweep.LAYOUTS for c in sweep.WIDTHS]
-# what the cap leaves out, from sizeof(XYZZ): 144 B (BN254 G1), 288, 224, 448 B per bucket
+# what the cap leaves out, from sizeof(XYZZ): 144 B (BN254 G1), 288, 224, 448 B per bucket; BLS12-381 has
+# BLS12-377's 14 limbs and, at c = 23 and 24, its window counts (12 and 11), hence the same three cases
 EXPECTED_OMITTED = {("bn254", True, "plain", 24), ("bls12377", False, "plain", 24),
-                    ("bls12377", True, "plain", 24), ("bls12377", True, "plain", 23)}
+                    ("bls12377", True, "plain", 24), ("bls12377", True, "plain", 23),
+                    ("bls12381", False, "plain", 24), ("bls12381", True, "plain", 24),
+                    ("bls12381", True, "plain", 23)}
 
 
 def klass(g):
@@ -86,8 +89,13 @@ def test_sweep_covers_every_class(table):
     print("run although above it:", over)
     assert omitted <= EXPECTED_OMITTED, sorted(omitted - EXPECTED_OMITTED)
     assert omitted == EXPECTED_OMITTED
-    # one GLV case lies above the cap too (6 windows of 2^23 buckets of 448 B); it runs
-    assert [k for k, _ in over] == [("bls12377", True, "glv", 24)] and over[0][1] < 32 << 30
+    assert all(lay == "plain" and c in (23, 24) for _, _, lay, c in omitted)
+    assert {k for k in omitted if k[0] == "bls12381"} == {
+        (cn, g2, lay, c) for cn, g2, lay, c in ALL
+        if cn == "bls12381" and lay == "plain" and sweep.case_alloc_bytes(cn, g2, lay, c) > sweep.MEM_CAP}
+    # one GLV case per 14-limb curve lies above the cap too (6 windows of 2^23 buckets of 448 B); they run
+    assert [k for k, _ in over] == [("bls12377", True, "glv", 24), ("bls12381", True, "glv", 24)]
+    assert all(alloc < 32 << 30 for _, alloc in over)
     # the shapes the suite did not run before: L = 8 and 16, no tree at all, four-level G2 trees
     Ls = {(k[2], g["L"]) for k, g in table.items() if k in run}
     assert {(lay, L) for lay in sweep.LAYOUTS for L in (2, 4, 8, 16, 32)} <= Ls
@@ -171,8 +179,13 @@ def recode(k, g):
 
 
 def glv_split(cname, k):
-    """(k1, k2) with k = k1 + k2 lambda, as the device computes them (tools/glv_constants.py)."""
+    """Signed (k1, k2) with k = k1 + k2 lambda mod r, as the device computes them
+    (tools/glv_constants.py): k1 >= 0 on BN254, both >= 0 on BLS12-377, either
+    sign for both on BLS12-381."""
     mod, d = sweep.glv_constants(cname)
+    if cname == "bls12381":
+        k1, n1, k2, n2 = mod.split_bls12381(k, d)
+        return (-k1 if n1 else k1), (-k2 if n2 else k2)
     return mod.split(k, d) if cname == "bn254" else mod.split_bls12377(k, d)
 
 
@@ -181,8 +194,8 @@ def digits(cname, layout, g, k):
     if layout != "glv":
         return [(w, d) for w, d in enumerate(recode(k, g)) if d]
     k1, k2 = glv_split(cname, k)
-    assert 0 <= k1 < 1 << 127 and abs(k2) < 1 << 127
-    out = [(w, d) for w, d in enumerate(recode(k1, g)) if d]
+    assert abs(k1) < 1 << 127 and abs(k2) < 1 << 127 and (k1 >= 0 or cname == "bls12381")
+    out = [(w, d if k1 >= 0 else -d) for w, d in enumerate(recode(abs(k1), g)) if d]
     return out + [(w, d if k2 >= 0 else -d) for w, d in enumerate(recode(abs(k2), g)) if d]
 
 
@@ -237,3 +250,67 @@ def test_structured_scalars_reach_the_edges(table, cname, g2):
                         k2_digits.update((w, d if k2 > 0 else -d) for w, d in enumerate(recode(abs(k2), g)) if d)
                 assert {w for w, _ in k2_digits} >= set(range(W - 1)), (c, sorted(k2_digits)[:4])
     print(cname, "g2" if g2 else "g1", "structured scalars over all cases:", total)
+
+
+# ---------------------------------------------------------------------------
+# BLS12-381: the GLV limit and the top window of a 255-bit scalar
+# ---------------------------------------------------------------------------
+def test_bls12381_scalars_below_the_glv_limit_split_trivially(table):
+    """The balanced split of BLS12-381 (tools/glv_constants.split_bls12381) rounds
+    k1 up only above (lambda - 1) / 2 and flips only above (r - 1) / 2; both lie
+    above glv_limit() = 2^126, so every one-digit scalar of the GLV cases splits
+    as (k, 0) with no sign on either half, as on the other curves."""
+    mod, d = sweep.glv_constants("bls12381")
+    lim = sweep.glv_limit()
+    assert lim == 1 << 126 and d["lam"] >> 1 >= lim and d["half"] >= lim
+    ks = {0, 1, 2, lim - 1, lim >> 1, (lim >> 1) + 1}
+    for c in sweep.WIDTHS:
+        ks.update(k for _, _, _, k in sweep.one_digit_scalars("bls12381", "glv", table[("bls12381", False, "glv", c)]))
+    assert len(ks) > 1000 and max(ks) < lim
+    for k in ks:
+        assert mod.split_bls12381(k, d) == (k, 0, 0, 0), k
+        assert glv_split("bls12381", k) == (k, 0)
+    # the first scalar that does not: k1 rounds up to -(lambda - 1) / 2
+    assert mod.split_bls12381((d["lam"] >> 1) + 1, d) == (d["lam"] >> 1, 1, 1, 0)
+
+
+@pytest.mark.parametrize("g2", [False, True])
+def test_bls12381_top_window_at_widths_dividing_255(table, g2):
+    """255 = 3 * 5 * 17: at c = 3, 5, 15 and 17 the windows below the top one
+    would hold all 255 bits of the scalar and leave the top window the carry
+    alone.  The plans cover bits + 1 = 256 bits exactly, so that happens only
+    where no window is narrowed: the plain layout at c = 17 (16 windows of 17
+    bits, excess 16 = W; msm_plan_geom narrows only below W), whose top window
+    starts at bit 255.  At c = 3, 5 and 15, and in the shared-bucket layout at
+    all four, the narrow windows pull the top window down to bit 254 or below,
+    so it holds scalar bits as well as the carry.  Either way the sweep's structured scalars reach digit 1
+    of the top window through a carry out of a negative digit below it, which is
+    the only way into a carry-only window; r - 1 is one of them."""
+    cname, r = "bls12381", pyref.CURVES["bls12381"].r
+    carry_only = set()
+    for layout in ("plain", "pre"):
+        for c in (3, 5, 15, 17):
+            g = table[(cname, g2, layout, c)]
+            W = g["W"]
+            assert W == 255 // c + 1
+            off, cw = sweep.window_geom(g, W - 1)
+            assert off + cw >= 256
+            if off >= 255:
+                carry_only.add((layout, c))
+                assert (g["narrow"], off, cw) == (0, 255, c)
+            else:
+                assert g["narrow"] == (c - 1 if c - 1 < W else W - 1) and off <= 254
+            by_carry = [k for k in sweep.structured_scalars(cname, layout, g)
+                        if k >> off == 0 and dict(digits(cname, layout, g, k)).get(W - 1) == 1]
+            assert by_carry, (layout, c)
+            assert all(dict(digits(cname, layout, g, k))[W - 2] < 0 for k in by_carry)
+            top = dict(digits(cname, layout, g, r - 1)).get(W - 1)
+            assert top == 1 if off >= 255 else top >= 1, (layout, c, top)
+    assert carry_only == {("plain", 17)}
+    # no other curve has a carry-only top window at these widths
+    for cn, g2_ in sweep.GROUPS:
+        for layout in ("plain", "pre"):
+            for c in (3, 5, 15, 17):
+                g = table[(cn, g2_, layout, c)]
+                off, _ = sweep.window_geom(g, g["W"] - 1)
+                assert (off >= sweep.FR_BITS[cn]) == ((cn, layout, c) == ("bls12381", "plain", 17))

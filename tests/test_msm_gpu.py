@@ -12,7 +12,8 @@ import pyref
 
 pytestmark = pytest.mark.gpu
 
-CASES = [("bn254", False), ("bn254", True), ("bls12377", False), ("bls12377", True)]
+CASES = [("bn254", False), ("bn254", True), ("bls12377", False), ("bls12377", True),
+         ("bls12381", False), ("bls12381", True)]
 
 
 def _edge_inputs(cname, g2, n, seed):
@@ -75,7 +76,7 @@ def test_msm_empty_and_single(gm_ctx, cname, g2, window):
 
 
 @pytest.mark.parametrize("value", [0, 1, "r-1"])
-@pytest.mark.parametrize("cname,g2", [("bn254", False), ("bls12377", True)])
+@pytest.mark.parametrize("cname,g2", [("bn254", False), ("bls12377", True), ("bls12381", False)])
 def test_msm_constant_scalars_c16(gm_ctx, oracle, cname, g2, value):
     """All scalars equal at c = 16: 0 (every digit is zero -- nothing enters the
     sort, all buckets empty), 1 (one bucket, all others empty) and r-1 (every
@@ -100,13 +101,14 @@ def test_msm_constant_scalars_c16(gm_ctx, oracle, cname, g2, value):
 
 
 def _random_points_host(ctx, cname, g2, n, seed):
-    import gnark_mi355x as gm
-    K = ctx.random_scalars(cname, n, seed)
-    P = ctx.batch_mul_base(cname, g2, gm.generator(cname, g2), K, n)
-    out = P.to_host()
-    K.free()
-    P.free()
-    return out
+    import device_points
+    return device_points.random_points_host(ctx, cname, g2, n, seed)
+
+
+def _points_of(ctx, cname, g2, K, n):
+    """Device buffer of [K_i]G (the oracle's table for BLS12-381, device_points.py)."""
+    import device_points
+    return device_points.batch_mul_generator(ctx, cname, g2, K, n)
 
 
 def test_msm_all_equal_points(gm_ctx, oracle):
@@ -127,13 +129,13 @@ def test_msm_all_equal_points(gm_ctx, oracle):
 
 
 @pytest.mark.parametrize("cname,g2,logn", [("bn254", False, 16), ("bn254", True, 13),
-                                           ("bls12377", False, 14), ("bls12377", True, 12)])
+                                           ("bls12377", False, 14), ("bls12377", True, 12),
+                                           ("bls12381", False, 14), ("bls12381", True, 12)])
 def test_msm_random_vs_oracle(gm_ctx, oracle, cname, g2, logn):
-    import gnark_mi355x as gm
     n = (1 << logn) + 37  # ragged size
     S = gm_ctx.random_scalars(cname, n, seed=0x5EED0002 + logn)
     K = gm_ctx.random_scalars(cname, n, seed=0x5EED1002 + logn)
-    P = gm_ctx.batch_mul_base(cname, g2, gm.generator(cname, g2), K, n)
+    P = _points_of(gm_ctx, cname, g2, K, n)
     sb = S.to_host()
     pb = P.to_host()
     _, aff = gm_ctx.msm(cname, S, P, n, g2)
@@ -195,6 +197,50 @@ def test_msm_huge_buckets_large(gm_ctx, oracle, cname, g2, logn):
         b.free()
 
 
+SKEW_CAP = 4096          # the skewed scalars are a prefix of this many
+SKEW_N_BLS12381 = 751    # bucket 1 of window 0 then holds 217 entries: slices 0..9 (test below)
+
+
+def _skewed_scalars(cname, n):
+    """The first n of SKEW_CAP wire-like scalars: {0, 1, 2, r - 1} drawn uniformly,
+    every hundredth replaced by a uniformly random one (test_msm_huge_buckets_large's
+    mix).  Canonical integers."""
+    c = pyref.CURVES[cname]
+    rng = np.random.default_rng(381)
+    vals = [(0, 1, 2, c.r - 1)[i] for i in rng.integers(0, 4, SKEW_CAP)]
+    vals[::100] = pyref.random_scalars(c, len(vals[::100]), 382)
+    return vals[:n]
+
+
+def test_msm_skewed_bls12381_smallest_long_span(gm_ctx, oracle):
+    """BLS12-381 G1 with the wire-like scalars at n = SKEW_N_BLS12381: by the
+    raw-bucket model (test_msm_raw_buckets_gpu._Layout: window 16, 24 entries per
+    accumulation slice, serial fixup up to 8 slices) this is the smallest prefix in
+    which a bucket spans more than 8 slices, i.e. the first that takes the tree
+    fixup (k_msm_fix_tree + k_msm_fixup_long) over 14-limb raw parts; at n - 1 no
+    bucket does.  Run at the model's window and, for the default plan, as is."""
+    import test_msm_raw_buckets_gpu as raw
+    cname, n = "bls12381", SKEW_N_BLS12381
+    assert raw.C == 16
+    sc = _skewed_scalars(cname, n)
+    assert raw._Layout(cname, False, sc, 0).long() and not raw._Layout(cname, False, sc[:-1], 0).long()
+    c = pyref.CURVES[cname]
+    sb = b"".join(pyref.encode_fr(c, v) for v in sc)
+    pb = _random_points_host(gm_ctx, cname, False, n, 0x381)
+    exp = oracle.msm(cname, False, sb, pb)
+    S, P = gm_ctx.copy_to_device(sb), gm_ctx.copy_to_device(pb)
+    try:
+        for window, glv in ((16, 0), (0, -1)):
+            gm_ctx.set_msm_window(window)
+            gm_ctx.set_msm_glv(glv)
+            assert gm_ctx.msm(cname, S, P, n, False)[1] == exp, (window, glv)
+    finally:
+        gm_ctx.set_msm_window(0)
+        gm_ctx.set_msm_glv(-1)
+        S.free()
+        P.free()
+
+
 @pytest.mark.parametrize("cname", ["bls12377", "bn254"])
 def test_kzg_commit_and_prepared_msm(gm_ctx, oracle, cname):
     """PLONK KZG commit (kzg.Commit over pk.Kzg.G1, backend/plonk/bls12-377/prove.go:
@@ -244,13 +290,13 @@ def test_msm_precomputed_edge_vs_pyref(gm_ctx, cname, g2):
 
 
 @pytest.mark.parametrize("cname,g2,logn", [("bn254", False, 16), ("bn254", True, 12),
-                                           ("bls12377", False, 14), ("bls12377", True, 11)])
+                                           ("bls12377", False, 14), ("bls12377", True, 11),
+                                           ("bls12381", False, 14), ("bls12381", True, 12)])
 def test_msm_precomputed_random_vs_oracle(gm_ctx, oracle, cname, g2, logn):
-    import gnark_mi355x as gm
     n = (1 << logn) + 37
     S = gm_ctx.random_scalars(cname, n, seed=0x5EED0005 + logn)
     K = gm_ctx.random_scalars(cname, n, seed=0x5EED1005 + logn)
-    P = gm_ctx.batch_mul_base(cname, g2, gm.generator(cname, g2), K, n)
+    P = _points_of(gm_ctx, cname, g2, K, n)
     sb, pb = S.to_host(), P.to_host()
     pre = gm_ctx.points_upload_precomputed(cname, pb, g2, 0)
     _, aff = gm_ctx.msm_precomputed(cname, S, pre, n, g2)
@@ -320,16 +366,16 @@ def test_msm_bucket_chain_special_cases(gm_ctx, cname, g2, window):
 
 
 @pytest.mark.parametrize("cname,g2,logn", [("bn254", False, 14), ("bn254", True, 12),
-                                           ("bls12377", False, 13), ("bls12377", True, 11)])
+                                           ("bls12377", False, 13), ("bls12377", True, 11),
+                                           ("bls12381", False, 13), ("bls12381", True, 11)])
 def test_msm_sort_geometries_vs_oracle(gm_ctx, oracle, cname, g2, logn):
     """Window sizes 8..20 give bucket counts from 2^12 to 13 * 2^19, i.e. every
     shape of the two-level bucket sort: one coarse bin covering all buckets
     (F >= log2 T), ~16K entries per coarse bin, and mostly empty buckets."""
-    import gnark_mi355x as gm
     n = (1 << logn) + 11
     S = gm_ctx.random_scalars(cname, n, seed=0x5EED0007 + logn)
     K = gm_ctx.random_scalars(cname, n, seed=0x5EED1007 + logn)
-    P = gm_ctx.batch_mul_base(cname, g2, gm.generator(cname, g2), K, n)
+    P = _points_of(gm_ctx, cname, g2, K, n)
     exp = oracle.msm(cname, g2, S.to_host(), P.to_host())
     for c in (16, 15, 8, 20):
         gm_ctx.set_msm_window(c)
@@ -361,16 +407,16 @@ def test_msm_split_coarse_bin(gm_ctx, oracle, value):
 
 
 @pytest.mark.parametrize("cname,g2,window,pre", [("bn254", False, 16, False), ("bn254", False, 0, True),
-                                                 ("bls12377", True, 0, False), ("bn254", True, 0, True)])
+                                                 ("bls12377", True, 0, False), ("bn254", True, 0, True),
+                                                 ("bls12381", False, 16, False), ("bls12381", True, 0, True)])
 def test_msm_three_level_sort_vs_oracle(gm_ctx, oracle, monkeypatch, cname, g2, window, pre):
     """The middle pass of the bucket sort (pass-1 super-bins split into coarse
     bins, msm_sort.hip) runs by itself only for large MSMs (2^22+, precomputed
     2^20+); GM_MSM_SORT_MING forces it here, at several depths."""
-    import gnark_mi355x as gm
     n = (1 << 14) + 11
     S = gm_ctx.random_scalars(cname, n, seed=0x3EED0007)
     K = gm_ctx.random_scalars(cname, n, seed=0x3EED1007)
-    P = gm_ctx.batch_mul_base(cname, g2, gm.generator(cname, g2), K, n)
+    P = _points_of(gm_ctx, cname, g2, K, n)
     exp = oracle.msm(cname, g2, S.to_host(), P.to_host())
     pts = gm_ctx.points_upload_precomputed(cname, P.to_host(), g2, window) if pre else None
     try:

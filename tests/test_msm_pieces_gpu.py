@@ -83,6 +83,7 @@ class _Plan:
 def env(gm_ctx, oracle):
     """Per curve: N random G1 points as host bytes, a larger MSM of another shape
     to dirty the workspace, and a cache of oracle results per (scalars, points)."""
+    import device_points
     import gnark_mi355x as gm
     st, exp = {}, {}
 
@@ -90,7 +91,7 @@ def env(gm_ctx, oracle):
         if cname not in st:
             n_big = (1 << 13) + 37
             K = gm_ctx.random_scalars(cname, n_big, seed=0xC0)
-            P = gm_ctx.batch_mul_base(cname, False, gm.generator(cname, False), K, n_big)
+            P = device_points.batch_mul_generator(gm_ctx, cname, False, K, n_big)
             S = gm_ctx.random_scalars(cname, n_big, seed=0xC8)
             K.free()
             st[cname] = (S, P, n_big, P.to_host()[: N * gm.point_bytes(cname, False)])
@@ -282,6 +283,15 @@ def test_bls12377_g1(gm_ctx, env, T):
     plan = _Plan(sc, T or T_DEFAULT)
     assert plan.long() if T == 4 else plan.cut()
     _run(gm_ctx, env, "bls12377", sc, T, dirty=True)
+
+
+@pytest.mark.parametrize("T", [4, 0])
+def test_bls12381_g1(gm_ctx, env, T):
+    """The same body over BLS12-381's 14-limb field (curve id 2)."""
+    sc = _uniform(2048, 32, seed=4) + []
+    plan = _Plan(sc, T or T_DEFAULT)
+    assert plan.long() if T == 4 else plan.cut()
+    _run(gm_ctx, env, "bls12381", sc, T, dirty=True)
 
 
 @pytest.mark.parametrize("T", [4, 0])

@@ -23,8 +23,8 @@ pytestmark = pytest.mark.gpu
 K_G1, K_G2, FIX_SERIAL, L_MAX = 24, 64, 8, 32
 C = 16          # forced window
 N = 1 << 12
-GROUPS = [("bn254", False), ("bn254", True), ("bls12377", False)]
-FR_BITS = {"bn254": 254, "bls12377": 253}
+GROUPS = [("bn254", False), ("bn254", True), ("bls12377", False), ("bls12381", False), ("bls12381", True)]
+FR_BITS = {"bn254": 254, "bls12377": 253, "bls12381": 255}
 
 
 def _digits(cname, k, glv):
@@ -104,6 +104,7 @@ class _Layout:
 @pytest.fixture(scope="module")
 def env(gm_ctx, oracle):
     """Per group: N random points (host bytes) and a larger random MSM to run first."""
+    import device_points
     import gnark_mi355x as gm
     st = {}
 
@@ -111,7 +112,7 @@ def env(gm_ctx, oracle):
         if (cname, g2) not in st:
             n_big = (1 << 13) + 37
             Kk = gm_ctx.random_scalars(cname, n_big, seed=0xB0 + g2)
-            P = gm_ctx.batch_mul_base(cname, g2, gm.generator(cname, g2), Kk, n_big)
+            P = device_points.batch_mul_generator(gm_ctx, cname, g2, Kk, n_big)
             S = gm_ctx.random_scalars(cname, n_big, seed=0xB8 + g2)
             Kk.free()
             pb = gm.point_bytes(cname, g2)

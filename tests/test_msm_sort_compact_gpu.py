@@ -15,9 +15,9 @@ import r1cs as R
 
 pytestmark = pytest.mark.gpu
 
-GROUPS = [("bn254", False), ("bn254", True), ("bls12377", False)]
+GROUPS = [("bn254", False), ("bn254", True), ("bls12377", False), ("bls12381", False), ("bls12381", True)]
 NMAX = (1 << 12) + 3
-FR_BITS = {"bn254": 254, "bls12377": 253}
+FR_BITS = {"bn254": 254, "bls12377": 253, "bls12381": 255}
 
 
 def _plain_geometry(cname, n, c):
@@ -64,14 +64,14 @@ def _shared_bits(n, stride, c, W, ming):
 def data(gm_ctx, oracle):
     """Per (curve, group): NMAX random scalars and points as host bytes, made
     once, and a cache of oracle results per input."""
-    import gnark_mi355x as gm
+    import device_points
     st, exp = {}, {}
 
     def get(cname, g2):
         if (cname, g2) not in st:
             S = gm_ctx.random_scalars(cname, NMAX, seed=0xC0DE + g2)
             K = gm_ctx.random_scalars(cname, NMAX, seed=0xC1DE + g2)
-            P = gm_ctx.batch_mul_base(cname, g2, gm.generator(cname, g2), K, NMAX)
+            P = device_points.batch_mul_generator(gm_ctx, cname, g2, K, NMAX)
             st[(cname, g2)] = (S.to_host(), P.to_host())
             for b in (S, K, P):
                 b.free()

@@ -5,8 +5,9 @@ Each window width c = 2..24 of gm_set_msm_window has its own reduction shape
 per node Q) and its own split of the scalar into full and narrow windows
 (msm_plan_geom), per curve, group and layout -- plain, GLV and shared-bucket
 precomputed.  The reduction walks all W * 2^(c-1) buckets whatever n is, so one
-MSM of a few thousand points per (group, layout, c) runs every shape; only four
-plain cases whose buckets, nodes and offsets exceed 16 GiB are left out (OMITTED).
+MSM of a few thousand points per (group, layout, c) runs every shape; only the
+plain cases at c = 23 and 24 whose buckets, nodes and offsets exceed 16 GiB are
+left out (OMITTED; test_msm_geometry.EXPECTED_OMITTED names them).
 
 Inputs of a case: structured scalars with one chosen digit +-b in one window,
 for every window and the edge buckets of the reduction (1, 2, L - 1, L, L + 1,
@@ -25,14 +26,15 @@ import pyref
 
 pytestmark = pytest.mark.gpu
 
-GROUPS = [("bn254", False), ("bn254", True), ("bls12377", False), ("bls12377", True)]
+GROUPS = [("bn254", False), ("bn254", True), ("bls12377", False), ("bls12377", True),
+          ("bls12381", False), ("bls12381", True)]
 LAYOUTS = ("plain", "glv", "pre")
 WIDTHS = tuple(range(2, 25))          # what gm_set_msm_window admits
 N_RANDOM = (1 << 12) + 37
 MEM_CAP = 16 << 30                    # bytes of buckets + nodes + offsets of one case
 TRIM_ABOVE = 2 << 30                  # cases above this give their arena back (gm_trim)
-FR_BITS = {"bn254": 254, "bls12377": 253}
-FP_LIMBS29 = {"bn254": 9, "bls12377": 14}   # radix-2^29 limbs of a base field element
+FR_BITS = {"bn254": 254, "bls12377": 253, "bls12381": 255}
+FP_LIMBS29 = {"bn254": 9, "bls12377": 14, "bls12381": 14}   # radix-2^29 limbs of a base field element
 
 
 def xyzz_bytes(cname, g2):
@@ -59,8 +61,8 @@ def case_alloc_bytes(cname, g2, layout, c):
 def sweep_cases():
     """(cname, g2, layout, c) of the sweep and of the cases the memory cap leaves
     out.  The cap applies to the plain layout, whose c = 23 and 24 reach 21 to 41
-    GB; GLV and precomputed cases all run (the largest, BLS12-377 G2 GLV at
-    c = 24, takes 25 GB)."""
+    GB; GLV and precomputed cases all run (the largest, the BLS12-377 and
+    BLS12-381 G2 GLV cases at c = 24, take 25 GB)."""
     run, omitted = [], []
     for cname, g2 in GROUPS:
         for layout in LAYOUTS:
@@ -103,8 +105,10 @@ def edge_buckets(g, w):
 
 
 def glv_limit():
-    """One-digit scalars below 2^126 split as (k, 0) on both curves: lambda of
-    BLS12-377 and r / b2 of BN254 lie above it (msm_impl.hpp GlvBn254, GlvBls377)."""
+    """One-digit scalars below 2^126 split as (k, 0) on every curve: lambda of
+    BLS12-377, r / b2 of BN254 and lambda / 2 of BLS12-381's balanced split lie
+    above it (msm_impl.hpp GlvBn254, GlvBls377, GlvBls381; test_msm_geometry.py
+    checks the last against tools/glv_constants.py)."""
     return 1 << 126
 
 
@@ -149,7 +153,8 @@ def glv_constants(cname):
             "glv_constants", os.path.join(os.path.dirname(__file__), "..", "tools", "glv_constants.py"))
         mod = importlib.util.module_from_spec(spec)
         spec.loader.exec_module(mod)
-        _GLV[cname] = (mod, mod.derive() if cname == "bn254" else mod.derive_bls12377())
+        derive = {"bn254": mod.derive, "bls12377": mod.derive_bls12377, "bls12381": mod.derive_bls12381}
+        _GLV[cname] = (mod, derive[cname]())
     return _GLV[cname]
 
 
@@ -167,6 +172,7 @@ _shared = {}
 def _group_inputs(ctx, cname, g2):
     """Host bytes: N_STRUCT_MAX points for the structured prefix, and the random
     tail (scalars, points) with the edge points of test_msm_gpu._edge_inputs."""
+    import device_points
     import gnark_mi355x as gm
     key = (cname, g2)
     if key not in _shared:
@@ -175,7 +181,7 @@ def _group_inputs(ctx, cname, g2):
         pbytes = gm.point_bytes(cname, g2)
         n = N_STRUCT_MAX + N_RANDOM
         K = ctx.random_scalars(cname, n, seed=0x5EED3000 + 2 * GROUPS.index(key))
-        P = ctx.batch_mul_base(cname, g2, gm.generator(cname, g2), K, n)
+        P = device_points.batch_mul_generator(ctx, cname, g2, K, n)
         S = ctx.random_scalars(cname, N_RANDOM, seed=0x5EED3001 + 2 * GROUPS.index(key))
         pb, sb = P.to_host(), bytearray(S.to_host())
         for b in (K, P, S):

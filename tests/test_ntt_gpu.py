@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 MODES = list(itertools.product([0, 1], [0, 1], [0, 1]))  # inverse, dit, coset
 
 
-@pytest.mark.parametrize("cname", ["bn254", "bls12377"])
+@pytest.mark.parametrize("cname", ["bn254", "bls12377", "bls12381"])
 @pytest.mark.parametrize("logn", [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18])
 def test_ntt_modes_vs_oracle(gm_ctx, oracle, cname, logn):
     n = 1 << logn
@@ -65,7 +65,7 @@ def _structured_vectors(cname, logn):
 # 8 + 8); 18: three passes (6 + 6 + 6) -- every pass shape, both even widths of the growing-bound rounds
 @pytest.mark.parametrize("inverse,dit,coset", MODES)
 @pytest.mark.parametrize("logn", [6, 7, 8, 12, 13, 14, 15, 16, 18])
-@pytest.mark.parametrize("cname", ["bn254", "bls12377"])
+@pytest.mark.parametrize("cname", ["bn254", "bls12377", "bls12381"])
 def test_ntt_structured_vs_oracle(gm_ctx, oracle, cname, logn, inverse, dit, coset):
     n = 1 << logn
     X = gm_ctx.malloc(32 * n)
@@ -78,7 +78,7 @@ def test_ntt_structured_vs_oracle(gm_ctx, oracle, cname, logn, inverse, dit, cos
         X.free()
 
 
-@pytest.mark.parametrize("cname", ["bn254", "bls12377"])
+@pytest.mark.parametrize("cname", ["bn254", "bls12377", "bls12381"])
 def test_ntt_small_vs_pyref(gm_ctx, cname):
     c = pyref.CURVES[cname]
     n = 16
@@ -109,7 +109,7 @@ def test_ntt_roundtrip_large(gm_ctx, logn):
     X.free()
 
 
-@pytest.mark.parametrize("cname", ["bn254", "bls12377"])
+@pytest.mark.parametrize("cname", ["bn254", "bls12377", "bls12381"])
 @pytest.mark.parametrize("length,n", [(3, 4), (13, 16), (1000, 1024), ((1 << 15) - 5, 1 << 15)])
 def test_compute_h_vs_oracle(gm_ctx, oracle, cname, length, n):
     A = gm_ctx.random_scalars(cname, n, seed=1 + length)

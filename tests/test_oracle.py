@@ -39,7 +39,7 @@ def test_bn254_twist_vectors_from_reference():
     assert G2.mul(on_not_sub, c.r) is not None  # not in the r-torsion subgroup
 
 
-@pytest.mark.parametrize("cname", ["bn254", "bls12377"])
+@pytest.mark.parametrize("cname", ["bn254", "bls12377", "bls12381"])
 def test_curve_constants(cname):
     c = pyref.CURVES[cname]
     for g2 in (False, True):
@@ -86,7 +86,7 @@ def test_oracle_msm_golden(oracle, name):
     assert got.hex() == g["expected_affine"]
 
 
-@pytest.mark.parametrize("cname", ["bn254", "bls12377"])
+@pytest.mark.parametrize("cname", ["bn254", "bls12377", "bls12381"])
 def test_oracle_ntt_golden(oracle, cname):
     g = _load("ntt_" + cname)
     x = bytes.fromhex(g["input"])
@@ -95,8 +95,8 @@ def test_oracle_ntt_golden(oracle, cname):
         assert oracle.fft(cname, x, inverse, dit, coset).hex() == exp, mode
 
 
-@pytest.mark.parametrize("name", ["h_cubic_bn254", "h_cubic_bls12377", "h_squaring15_bn254",
-                                  "h_squaring15_bls12377"])
+@pytest.mark.parametrize("name", ["h_cubic_bn254", "h_cubic_bls12377", "h_cubic_bls12381", "h_squaring15_bn254",
+                                  "h_squaring15_bls12377", "h_squaring15_bls12381"])
 def test_oracle_compute_h_golden(oracle, name):
     g = _load(name)
     got = oracle.compute_h(g["curve"], bytes.fromhex(g["a"]), bytes.fromhex(g["b"]), bytes.fromhex(g["c"]), g["n"])
@@ -113,7 +113,7 @@ def _pk_from_fixture(g):
     return pk
 
 
-@pytest.mark.parametrize("cname", ["bn254", "bls12377"])
+@pytest.mark.parametrize("cname", ["bn254", "bls12377", "bls12381"])
 def test_oracle_groth16_golden(oracle, cname):
     g = _load("groth16_cubic_" + cname)
     pk = _pk_from_fixture(g)
@@ -124,7 +124,7 @@ def test_oracle_groth16_golden(oracle, cname):
     assert oracle.g16_check(cname, r1, h("toxic"), h("wires"), h("r"), h("s"), ar, bs, krs) == 7
 
 
-@pytest.mark.parametrize("cname", ["bn254", "bls12377"])
+@pytest.mark.parametrize("cname", ["bn254", "bls12377", "bls12381"])
 def test_oracle_setup_matches_pyref(oracle, cname):
     """The C++ Setup restatement reproduces the pure-Python one (fixture pk)."""
     g = _load("groth16_cubic_" + cname)
@@ -136,7 +136,7 @@ def test_oracle_setup_matches_pyref(oracle, cname):
 
 # ---- C++ restatement vs pyref at random sizes -------------------------------------
 
-@pytest.mark.parametrize("cname", ["bn254", "bls12377"])
+@pytest.mark.parametrize("cname", ["bn254", "bls12377", "bls12381"])
 def test_oracle_pippenger_vs_naive(oracle, cname):
     c = pyref.CURVES[cname]
     n = 300
@@ -147,7 +147,7 @@ def test_oracle_pippenger_vs_naive(oracle, cname):
     assert oracle.msm(cname, False, sb, pts) == oracle.msm(cname, False, sb, pts, naive=True)
 
 
-@pytest.mark.parametrize("cname", ["bn254", "bls12377"])
+@pytest.mark.parametrize("cname", ["bn254", "bls12377", "bls12381"])
 def test_oracle_groth16_random_circuit(oracle, cname):
     r1, W = R.squaring_chain(200, cname, x=7)
     tox = R.encode_vec(cname, [11, 22, 33, 44, 55])
@@ -157,6 +157,124 @@ def test_oracle_groth16_random_circuit(oracle, cname):
     rb, sb = enc([3]), enc([4])
     proof = oracle.g16_prove(cname, pk, r1.nb_public, enc(W), enc(a), enc(b), enc(cc), rb, sb)
     assert oracle.g16_check(cname, r1, tox, enc(W), rb, sb, *proof) == 7
+
+
+# ---- BLS12-381 (curve id 2): the C++ restatement pinned to pyref ----------------
+
+def _enc_pts(c, pts, g2):
+    return b"".join(pyref.encode_point(c, P, g2) for P in pts)
+
+
+@pytest.mark.parametrize("g2", [False, True])
+def test_oracle_bls12381_generators_are_the_published_ones(oracle, g2):
+    import bls12381_params as bp
+    assert bp.C is pyref.CURVES["bls12381"]
+    want = bp.G2_GEN if g2 else bp.G1_GEN
+    assert oracle.generator("bls12381", g2) == pyref.encode_point(bp.C, want, g2)
+    assert pyref.Group(bp.C, g2).generator() == want
+
+
+@pytest.mark.parametrize("cname,g2", [("bn254", False), ("bls12377", True), ("bls12381", False), ("bls12381", True)])
+def test_oracle_msm_edge_set_vs_pyref(oracle, cname, g2):
+    """Infinity, scalars 0, 1 and r-1, a duplicate, P and -P, k and r-k: the
+    signed Pippenger, the unsigned one and the naive sum against pyref."""
+    from test_msm_gpu import _edge_inputs
+    c = pyref.CURVES[cname]
+    sc, pts = _edge_inputs(cname, g2, 20, 500 + g2)
+    exp = pyref.encode_point(c, pyref.Group(c, g2).msm(sc, pts), g2)
+    sb, pb = R.encode_vec(cname, sc), _enc_pts(c, pts, g2)
+    for naive in (False, True, 2):
+        assert oracle.msm(cname, g2, sb, pb, naive=naive) == exp, naive
+
+
+@pytest.mark.parametrize("n", [1, 2, 16])
+@pytest.mark.parametrize("cname", ["bn254", "bls12377", "bls12381"])
+def test_oracle_fft_all_modes_vs_pyref(oracle, cname, n):
+    c = pyref.CURVES[cname]
+    vals = pyref.random_scalars(c, n, 40 + n)
+    xb = R.encode_vec(cname, vals)
+    for inverse in (0, 1):
+        for dit in (0, 1):
+            for coset in (0, 1):
+                fn = pyref.fft_inverse if inverse else pyref.fft
+                exp = fn(c, vals, "DIT" if dit else "DIF", bool(coset))
+                assert oracle.fft(cname, xb, inverse, dit, coset) == R.encode_vec(cname, exp), (inverse, dit, coset)
+
+
+@pytest.mark.parametrize("length,n", [(3, 4), (13, 16)])
+@pytest.mark.parametrize("cname", ["bn254", "bls12377", "bls12381"])
+def test_oracle_compute_h_vs_pyref(oracle, cname, length, n):
+    c = pyref.CURVES[cname]
+    a, b, cc = (pyref.random_scalars(c, length, 60 + 3 * n + i) for i in range(3))
+    exp = pyref.compute_h(c, a, b, cc, n)
+    enc = lambda v: R.encode_vec(cname, v)
+    assert oracle.compute_h(cname, enc(a), enc(b), enc(cc), n) == enc(exp)
+
+
+@pytest.mark.parametrize("cname,g2", [("bn254", False), ("bls12377", True), ("bls12381", False), ("bls12381", True)])
+def test_oracle_batch_mul_base_vs_pyref(oracle, cname, g2):
+    c = pyref.CURVES[cname]
+    G = pyref.Group(c, g2)
+    ks = [0, 1, 2, c.r - 1, 255, 256, (1 << 248) + 1] + pyref.random_scalars(c, 5, 70 + g2)
+    base = G.mul(G.generator(), 0xB45E)
+    got = oracle.batch_mul_base(cname, g2, pyref.encode_point(c, base, g2), R.encode_vec(cname, ks))
+    assert got == _enc_pts(c, [G.mul(base, k) for k in ks], g2)
+
+
+@pytest.mark.parametrize("circuit", ["cubic", "squaring15"])
+def test_oracle_bls12381_groth16_vs_pyref(oracle, circuit):
+    """Setup array for array and the proof point for point against pyref; the
+    exponent check accepts the proof and rejects it for another witness."""
+    import bls12381_params as bp
+    cname, c = "bls12381", pyref.CURVES["bls12381"]
+    r1, W = R.cubic_circuit(cname) if circuit == "cubic" else R.squaring_chain(15, cname, x=5)
+    toxic = [0x71C3, 0xA1FA, 0xBE7A, 0x6A33A, 0xDE17A]
+    r_, s_ = 0x1357, 0x2468
+    ref = pyref.g16_setup(c, r1.cons, r1.nb_wires, r1.nb_public, toxic)
+    enc = lambda v: R.encode_vec(cname, v)
+    pk = oracle.g16_setup(cname, r1, enc(toxic))
+    for k, v in bp.pk_bytes(ref).items():
+        assert pk[k].tobytes() == bytes(v), k
+    a, b, cc = r1.solve_abc(W)
+    ar, bs, krs = pyref.g16_prove(c, ref, W, a, b, cc, r_, s_)
+    got = oracle.g16_prove(cname, pk, r1.nb_public, enc(W), enc(a), enc(b), enc(cc), enc([r_]), enc([s_]))
+    assert got == (pyref.encode_point(c, ar, False), pyref.encode_point(c, bs, True), pyref.encode_point(c, krs, False))
+    assert oracle.g16_check(cname, r1, enc(toxic), enc(W), enc([r_]), enc([s_]), *got) == 7
+    bad = list(W)
+    bad[2] += 1
+    assert oracle.g16_check(cname, r1, enc(toxic), enc(bad), enc([r_]), enc([s_]), *got) != 7
+
+
+@pytest.mark.parametrize("g2", [False, True])
+def test_oracle_bls12381_msm_4096_vs_known_logs(oracle, g2):
+    """2^12 uniformly random points [k_i]G from the fixed-base table: the MSM is
+    [sum s_i k_i]G, one pyref scalar multiplication."""
+    cname, c = "bls12381", pyref.CURVES["bls12381"]
+    n = 1 << 12
+    ks, sc = pyref.random_scalars(c, n, 81 + g2), pyref.random_scalars(c, n, 83 + g2)
+    pts = oracle.batch_mul_base(cname, g2, oracle.generator(cname, g2), R.encode_vec(cname, ks))
+    G = pyref.Group(c, g2)
+    exp = pyref.encode_point(c, G.mul(G.generator(), sum(s * k for s, k in zip(sc, ks)) % c.r), g2)
+    assert oracle.msm(cname, g2, R.encode_vec(cname, sc), pts) == exp
+    assert oracle.msm(cname, g2, R.encode_vec(cname, sc), pts, naive=2) == exp
+
+
+def test_oracle_bls12381_fft_roundtrip_2p18(oracle):
+    """FFT then FFTInverse at 2^18 is the identity, on and off the coset, and a
+    transform of that size stays far below the second the GPU suites, which call
+    it some hundred times, can afford (the bound is loose: a sanity check)."""
+    import time
+    import numpy as np
+    n = 1 << 18
+    rng = np.random.default_rng(18)
+    x = rng.integers(0, 1 << 62, (n, 4), dtype=np.uint64)  # < 2^254 < r: valid Montgomery residues
+    xb = x.tobytes()
+    for coset in (0, 1):
+        t0 = time.perf_counter()
+        y = oracle.fft("bls12381", xb, 0, 0, coset)
+        dt = time.perf_counter() - t0
+        assert y != xb and oracle.fft("bls12381", y, 1, 1, coset) == xb
+        assert dt < 5.0, dt
 
 
 # ---- BSB22 commitments (prove.go:82-139) --------------------------------------
@@ -178,7 +296,7 @@ def test_bsb22_serialization_shapes():
     """SerializeCommitment (constraint/commitment.go:70-82) = Marshal(D) (the
     uncompressed point, verify.go:88) || each committed public value as
     (fr.Bits-1)/8+1 big-endian bytes; fr.Hash takes 16 + 32 = 48 bytes per element."""
-    for cname in ("bn254", "bls12377"):
+    for cname in ("bn254", "bls12377", "bls12381"):
         c = pyref.CURVES[cname]
         G = pyref.Group(c, False)
         D = G.mul(G.generator(), 12345)
@@ -190,7 +308,7 @@ def test_bsb22_serialization_shapes():
         assert len(v) == 2 and all(0 <= x < c.r for x in v) and v[0] != v[1]
 
 
-@pytest.mark.parametrize("cname,ncommit", [("bn254", 1), ("bn254", 2), ("bls12377", 2)])
+@pytest.mark.parametrize("cname,ncommit", [("bn254", 1), ("bn254", 2), ("bls12377", 2), ("bls12381", 1)])
 def test_oracle_groth16_bsb22_verifies(oracle, cname, ncommit):
     """The oracle's prover with BSB22 commitments (hint override, Pedersen
     commit / proof of knowledge, fold, K filter) produces proofs that satisfy
@@ -217,7 +335,8 @@ def test_oracle_groth16_bsb22_verifies(oracle, cname, ncommit):
     assert not oracle.bsb22_check(cname, r1, pk, info, nf, sig)
 
 
-@pytest.mark.parametrize("cname,g2", [("bn254", False), ("bn254", True), ("bls12377", False), ("bls12377", True)])
+@pytest.mark.parametrize("cname,g2", [("bn254", False), ("bn254", True), ("bls12377", False), ("bls12377", True),
+                                      ("bls12381", False), ("bls12381", True)])
 def test_oracle_signed_pippenger_vs_unsigned(oracle, cname, g2):
     """The default oracle MSM (signed digits, XYZZ buckets: gnark-crypto
     MultiExp's shape; the bench's CPU baseline) against the unsigned-digit

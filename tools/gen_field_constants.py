@@ -15,9 +15,7 @@ Writes two independent headers so that the product (device + host code) and
 the test oracle never share a source file:
 
   gnark-icicle_amd/csrc/field_constants.hpp   (product)
-  oracle/oracle_constants.h                   (test oracle; BN254 and BLS12-377
-                                               only: the C++ oracle does not know
-                                               BLS12-381, whose reference is pyref)
+  oracle/oracle_constants.h                   (test oracle)
 
 Run:  python tools/gen_field_constants.py
 """
@@ -33,9 +31,9 @@ FIELDS = {
     "BLS12381_FP": (0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab, 6),
     "BLS12381_FR": (0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001, 4),
 }
-# the fields and generators the test oracle's header carries (never extended)
-ORACLE_FIELDS = ("BN254_FP", "BN254_FR", "BLS12377_FP", "BLS12377_FR")
-ORACLE_GENERATORS = ("BN254_G1", "BN254_G2", "BLS12377_G1", "BLS12377_G2")
+# the fields and generators the test oracle's header carries
+ORACLE_FIELDS = ("BN254_FP", "BN254_FR", "BLS12377_FP", "BLS12377_FR", "BLS12381_FP", "BLS12381_FR")
+ORACLE_GENERATORS = ("BN254_G1", "BN254_G2", "BLS12377_G1", "BLS12377_G2", "BLS12381_G1", "BLS12381_G2")
 
 
 # curve generators, canonical coordinates (gnark-crypto curve.Generators())
