@@ -25,6 +25,7 @@
 #include "points_codec.hpp"
 #include "msm.hpp"
 #include "ntt.hpp"
+#include "pairing.hpp"
 #include "runtime.hpp"
 
 namespace gm {
@@ -1392,6 +1393,69 @@ int gm_points_encode(gm_ctx* ctx, int curve, int g2, int encoding, const void* p
   *not_reduced = 0;
   if (n == 0) return GM_OK;
   return points_encode_device(ctx, curve, g2 != 0, encoding == GM_ENC_RAW, points_dev, n, enc_dev, not_reduced);
+}
+
+// ---- pairing-product checks and Groth16 verification (pairing.hip) -----------------------
+static int pairing_refusals(const char* me, gm_ctx* ctx, int curve, const void* g1, const void* g2, size_t n_products,
+                            size_t k, const uint8_t* ok_out, bool device) {
+  if (int rc = check_curve(curve, CURVES_ALL, me)) return rc;
+  if (!ctx || !g1 || !g2 || !ok_out) return refuse_null(me);
+  if (k == 0) return codec_refuse(me, "k must be at least 1");
+  if (device && ((uintptr_t)g1 % 16 || (uintptr_t)g2 % 16)) return codec_refuse(me, "the points must be 16-byte aligned");
+  if (n_products && k > (~size_t(0)) / pairing_gt_bytes(curve) / n_products)
+    return codec_refuse(me, "n_products * k pairs do not fit the address space");
+  return GM_OK;
+}
+
+int gm_pairing_check(gm_ctx* ctx, int curve, const void* g1_host, const void* g2_host, size_t n_products, size_t k,
+                     uint8_t* ok_out) {
+  if (int rc = pairing_refusals("gm_pairing_check", ctx, curve, g1_host, g2_host, n_products, k, ok_out, false)) return rc;
+  if (n_products == 0) return GM_OK;
+  return pairing_check_host(ctx, curve, g1_host, g2_host, n_products, k, ok_out);
+}
+
+int gm_pairing_check_device(gm_ctx* ctx, int curve, const void* g1_dev, const void* g2_dev, size_t n_products,
+                            size_t k, uint8_t* ok_out) {
+  if (int rc = pairing_refusals("gm_pairing_check_device", ctx, curve, g1_dev, g2_dev, n_products, k, ok_out, true))
+    return rc;
+  if (n_products == 0) return GM_OK;
+  return pairing_check_device(ctx, curve, g1_dev, g2_dev, n_products, k, ok_out);
+}
+
+int gm_g16_vk_upload(gm_ctx* ctx, int curve, const gm_g16_vk_host* vk, gm_g16_vk** out) {
+  const char* me = "gm_g16_vk_upload";
+  if (int rc = check_curve(curve, CURVES_ALL, me)) return rc;
+  if (!ctx || !vk || !out) return refuse_null(me);
+  *out = nullptr;
+  if (!vk->alpha_g1 || !vk->beta_g2 || !vk->gamma_g2 || !vk->delta_g2 || !vk->k_g1) return refuse_null(me);
+  if (vk->nb_k == 0) return codec_refuse(me, "nb_k must be at least 1 (K[0], the one wire)");
+  return g16_vk_upload(ctx, curve, vk, out);
+}
+
+int gm_g16_vk_free(gm_ctx* ctx, gm_g16_vk* vk) {
+  if (!ctx || !vk) return refuse_null("gm_g16_vk_free");
+  if (vk->ctx != ctx) return codec_refuse("gm_g16_vk_free", "the key belongs to another context");
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  GM_HIP(hipStreamSynchronize(ctx->stream));
+  if (vk->g1) hipFree(vk->g1);
+  if (vk->g2) hipFree(vk->g2);
+  delete vk;
+  return GM_OK;
+}
+
+int gm_g16_verify_batch(gm_ctx* ctx, const gm_g16_vk* vk, const void* proofs_host, const void* publics_host, size_t m,
+                        uint8_t* status_out, size_t* nb_ok) {
+  const char* me = "gm_g16_verify_batch";
+  if (!ctx || !vk) return refuse_null(me);
+  if (vk->ctx != ctx) return codec_refuse(me, "the key belongs to another context");
+  if (m == 0) {
+    if (nb_ok) *nb_ok = 0;
+    return GM_OK;
+  }
+  if (!proofs_host || !status_out || (vk->nb_k > 1 && !publics_host)) return refuse_null(me);
+  if (m > (~size_t(0)) / (16 * fp_bytes(vk->curve))) return codec_refuse(me, "m proofs do not fit the address space");
+  return g16_verify_batch(ctx, vk, proofs_host, publics_host, m, status_out, nb_ok);
 }
 
 // ---- Groth16 setup: fixed-base batch multiplication (g16_setup.hip) --------------------

@@ -69,11 +69,12 @@ SYMBOLS = [
     "gm_points_check", "gm_points_check_host", "gm_set_points_check_chunk", "gm_g16_pk_check",
     "gm_g16_pk_check_dump",
     "gm_points_decode", "gm_points_decode_host", "gm_points_encode", "gm_g16_pk_upload_encoded",
+    "gm_pairing_check", "gm_pairing_check_device", "gm_g16_vk_upload", "gm_g16_vk_free", "gm_g16_verify_batch",
 ]
 # test-only library (include/gnark_mi355x_testhooks.h, libgnark_mi355x_testhooks.so)
 TEST_SYMBOLS = ["gm_test_field_op", "gm_test_point_op", "gm_test_stage_replay_chain",
                 "gm_test_msm_g2_keyless_plan", "gm_test_field_raw_op", "gm_test_point_raw_op",
-                "gm_test_msm_geometry", "gm_test_scan", "gm_test_fe_sqrt"]
+                "gm_test_msm_geometry", "gm_test_scan", "gm_test_fe_sqrt", "gm_test_pairing_op"]
 TESTHOOKS_PATH = os.path.join(os.path.dirname(LIB_PATH), "libgnark_mi355x_testhooks.so")
 
 
@@ -254,6 +255,17 @@ TGEOM_MAX_LEVELS = 24
 FE_SQRT_HOOK_BLOCK = 64
 
 
+class _G16VkHost(ctypes.Structure):
+    _fields_ = [("alpha_g1", ctypes.c_void_p), ("beta_g2", ctypes.c_void_p), ("gamma_g2", ctypes.c_void_p),
+                ("delta_g2", ctypes.c_void_p), ("k_g1", ctypes.c_void_p), ("nb_k", ctypes.c_size_t)]
+
+
+# gm_test_pairing_op ops; gm_g16_verify_batch status bytes
+(TPAIR_MUL, TPAIR_SQR, TPAIR_INV, TPAIR_CONJ, TPAIR_FROB1, TPAIR_FROB2, TPAIR_CYC_SQR, TPAIR_LINE_MUL, TPAIR_EXP_U,
+ TPAIR_MILLER, TPAIR_FINAL_EXP) = range(11)
+G16_VERIFY_OK, G16_VERIFY_BAD_POINT, G16_VERIFY_MISMATCH, G16_VERIFY_BAD_INPUT = 0, 1, 2, 3
+
+
 class _MsmGeom(ctypes.Structure):
     """gm_test_msm_geom (include/gnark_mi355x_testhooks.h)."""
     _fields_ = ([(k, ctypes.c_uint32) for k in ("c", "W", "wn", "narrow", "Wred", "nb", "total", "glv", "shared",
@@ -288,6 +300,7 @@ def load_testhooks(path: str = None):
     T.gm_test_msm_geometry.argtypes = [i, i, sz, i, i, ctypes.POINTER(_MsmGeom)]
     T.gm_test_scan.argtypes = [vp, i, vp, sz, vp]
     T.gm_test_fe_sqrt.argtypes = [vp, i, i, vp, sz, vp, vp]
+    T.gm_test_pairing_op.argtypes = [vp, i, i, vp, vp, sz, vp]
     _testhooks = T
     return T
 
@@ -433,6 +446,11 @@ def load_library(path: str = LIB_PATH):
     L.gm_points_encode.argtypes = [vp, i, i, i, vp, sz, vp, ctypes.POINTER(u64)]
     L.gm_g16_pk_upload_encoded.argtypes = [vp, i, vp, i, u64, i, ctypes.c_uint, vp,
                                            ctypes.POINTER(_G16PkDecodeReport), ctypes.POINTER(u64), pvp]
+    L.gm_pairing_check.argtypes = [vp, i, vp, vp, sz, sz, vp]
+    L.gm_pairing_check_device.argtypes = [vp, i, vp, vp, sz, sz, vp]
+    L.gm_g16_vk_upload.argtypes = [vp, i, ctypes.POINTER(_G16VkHost), pvp]
+    L.gm_g16_vk_free.argtypes = [vp, vp]
+    L.gm_g16_verify_batch.argtypes = [vp, vp, vp, vp, sz, vp, psz]
     _lib = L
     return L
 
@@ -598,6 +616,42 @@ class Context:
         _check(load_library().gm_points_check_host(self.handle, curve_id(curve), int(g2), _p(a),
                                                    a.size // point_bytes(curve, g2), ctypes.byref(rep)))
         return rep.as_dict()
+
+    # ---- pairing-product checks ---------------------------------------------
+    def pairing_check(self, curve, g1, g2, k: int) -> np.ndarray:
+        """gm_pairing_check: gnark points in host memory, products of k pairs each;
+        one byte per product, 1 where the product of pairings is 1."""
+        a, b = _buf(g1), _buf(g2)
+        n = a.size // point_bytes(curve, False)
+        assert k and n % k == 0 and b.size // point_bytes(curve, True) == n
+        ok = np.full(max(n // k, 1), 0xEE, np.uint8)
+        _check(load_library().gm_pairing_check(self.handle, curve_id(curve), _p(a), _p(b), n // k, k, _p(ok)))
+        return ok[:n // k]
+
+    def pairing_check_device(self, curve, g1: DeviceBuffer, g2: DeviceBuffer, n_products: int, k: int) -> np.ndarray:
+        ok = np.full(max(n_products, 1), 0xEE, np.uint8)
+        _check(load_library().gm_pairing_check_device(self.handle, curve_id(curve), g1.ptr, g2.ptr, n_products, k,
+                                                      _p(ok)))
+        return ok[:n_products]
+
+    def test_pairing_op(self, curve, op: int, a: bytes, b: bytes | None, n: int, guard: int = 64) -> bytes:
+        """gm_test_pairing_op over n elements; the output buffer carries `guard`
+        bytes of 0xA5 behind it, which must come back untouched."""
+        out_bytes = n * 12 * FP_BYTES[curve_id(curve)]
+        A = self.copy_to_device(a)
+        B = self.copy_to_device(b) if b else None
+        O = self.copy_to_device(bytes([0xA5]) * (out_bytes + guard))
+        try:
+            _check(load_testhooks().gm_test_pairing_op(self.handle, curve_id(curve), op, A.ptr, B.ptr if B else None, n,
+                                                       O.ptr))
+            got = O.to_host()
+            if got[out_bytes:] != bytes([0xA5]) * guard:
+                raise GmError("gm_test_pairing_op wrote behind its output")
+            return got[:out_bytes]
+        finally:
+            for x in (A, B, O):
+                if x is not None:
+                    x.free()
 
     def set_points_check_chunk(self, nbytes: int):
         """Test knob: the chunk of the streamed point checks (0 = the default)."""
@@ -1478,6 +1532,38 @@ class ProvingKey:
         _check(load_library().gm_g16_prove_partial(self.ctx.handle, self.handle, wires.ptr, a.ptr, b.ptr, c.ptr,
                                                    nb_constraints, _p(out)))
         return out.tobytes()
+
+
+class VerifyingKey:
+    """A Groth16 verifying key resident on the device (gm_g16_vk_upload).  vk: gnark
+    point bytes alpha_g1, beta_g2, gamma_g2, delta_g2 and k_g1 (nb_k points)."""
+
+    def __init__(self, ctx: Context, curve, vk: dict):
+        self.ctx, self.curve = ctx, curve_id(curve)
+        arrs = {k: _buf(vk[k]) for k in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "k_g1")}
+        self.nb_k = arrs["k_g1"].size // point_bytes(curve, False)
+        host = _G16VkHost(*[arrs[k].ctypes.data for k in ("alpha_g1", "beta_g2", "gamma_g2", "delta_g2", "k_g1")],
+                          self.nb_k)
+        h = ctypes.c_void_p()
+        _check(load_library().gm_g16_vk_upload(ctx.handle, self.curve, ctypes.byref(host), ctypes.byref(h)))
+        self.handle = h
+
+    def verify_batch(self, proofs, publics) -> tuple[np.ndarray, int]:
+        """gm_g16_verify_batch: proofs = m records Ar | Bs | Krs (gnark points),
+        publics = m x (nb_k - 1) Montgomery fr.Elements; (status bytes, accepted)."""
+        a, b = _buf(proofs), _buf(publics)
+        m = a.size // (8 * FP_BYTES[self.curve])
+        assert b.size == m * (self.nb_k - 1) * FR_BYTES
+        st = np.full(max(m, 1), 0xEE, np.uint8)
+        nb_ok = ctypes.c_size_t(0)
+        _check(load_library().gm_g16_verify_batch(self.ctx.handle, self.handle, _p(a), _p(b) if b.size else None, m,
+                                                  _p(st), ctypes.byref(nb_ok)))
+        return st[:m], int(nb_ok.value)
+
+    def free(self):
+        if self.handle:
+            _check(load_library().gm_g16_vk_free(self.ctx.handle, self.handle))
+            self.handle = None
 
 
 class PendingMsm:

@@ -1101,6 +1101,62 @@ int gm_g16_pk_upload_encoded(gm_ctx* ctx, int curve, const gm_g16_pk_host* meta,
                              int encoding, unsigned flags, void* singles_out, gm_g16_pk_decode_report* report,
                              uint64_t* end_offset, gm_g16_pk** pk);
 
+/* ---- pairing-product checks and batched Groth16 verification ---------------------
+ * The optimal ate pairing of gnark-crypto on all three curve ids (DESIGN.md
+ * section 3.11): one lane per pair runs the Miller loop, the Miller values of a
+ * product are multiplied 16 per lane and launch, and one lane per product runs
+ * the final exponentiation.  No entry returns a GT element.
+ *
+ * gm_pairing_check: n_products products of k pairs each,
+ *   ok_out[j] = (prod_{i<k} e(g1[j k + i], g2[j k + i]) == 1)   (1 or 0).
+ * The points are gnark affine points and are assumed on the curve and in the
+ * subgroup (gm_points_check); a pair with either point at infinity, (0, 0),
+ * contributes 1.  The host variant streams the arrays in chunks of whole
+ * products and keeps no host pointer; the device variant takes device arrays
+ * (16-byte aligned) and writes ok_out on the host.  The workspace of a call
+ * grows with k (one Fp12 value per pair of a chunk).
+ * GM_ERR_INVALID, before any launch: an unknown curve id ("unknown curve id"), a
+ * NULL context or array, k == 0, a misaligned device array, n_products * k not
+ * fitting the address space.  n_products == 0: GM_OK with nothing written. */
+int gm_pairing_check(gm_ctx* ctx, int curve, const void* g1_host, const void* g2_host, size_t n_products, size_t k,
+                     uint8_t* ok_out);
+int gm_pairing_check_device(gm_ctx* ctx, int curve, const void* g1_dev, const void* g2_dev, size_t n_products,
+                            size_t k, uint8_t* ok_out /* host */);
+
+/* A Groth16 verifying key resident on the device.  The members are gnark affine
+ * points in host memory: G1 alpha, G2 beta, gamma, delta, and the nb_k points of
+ * G1.K (nb_k = public inputs + 1, the one wire included).  gm_g16_vk_upload runs
+ * the point check on every member and refuses the key with GM_ERR_INVALID, naming
+ * the member and the class, if one fails; it keeps -alpha, beta, -gamma, -delta
+ * and K on the device and no host pointer.  A verifying key with BSB22 commitments
+ * (CommitmentKeys, PublicAndCommitmentCommitted) has no field here: such keys are
+ * not served.  Free the key before gm_destroy.  GM_ERR_INVALID: an unknown curve
+ * id, a NULL argument or member, nb_k == 0. */
+typedef struct gm_g16_vk gm_g16_vk;
+typedef struct {
+  const void *alpha_g1, *beta_g2, *gamma_g2, *delta_g2, *k_g1;
+  size_t nb_k;
+} gm_g16_vk_host;
+int gm_g16_vk_upload(gm_ctx* ctx, int curve, const gm_g16_vk_host* vk, gm_g16_vk** out);
+int gm_g16_vk_free(gm_ctx* ctx, gm_g16_vk* vk);
+/* m proofs against one key in the same launches.  proofs_host: m records
+ * {Ar G1Affine, Bs G2Affine, Krs G1Affine} (gnark's in-memory Proof without
+ * commitments); publics_host: m x (nb_k - 1) fr.Elements in gnark Montgomery form
+ * (may be NULL when nb_k == 1).  Per proof: Ar, Krs and Bs are classed by the point
+ * check as proof.isValid does (backend/groth16/bn254/verify.go:67), kSum = K[0] +
+ * sum_j x_j K[j + 1] is computed, and e(Ar, Bs) e(Krs, -delta) e(kSum, -gamma)
+ * e(-alpha, beta) == 1 is checked: four Miller lanes and one final exponentiation.
+ * status_out[i]: GM_G16_VERIFY_OK, _BAD_POINT (a proof point failed the point
+ * check), _MISMATCH (the pairing equation fails) or _BAD_INPUT (a public input's
+ * words are not below r); the first that applies in the order BAD_POINT,
+ * BAD_INPUT, MISMATCH.  *nb_ok (may be NULL) counts the accepted proofs.  A bad
+ * proof never fails the call.  The arrays are streamed in chunks of whole proofs;
+ * no host pointer is kept.  GM_ERR_INVALID: a NULL context, key, array or
+ * status_out, a key of another context.  m == 0: GM_OK with nothing written. */
+enum { GM_G16_VERIFY_OK = 0, GM_G16_VERIFY_BAD_POINT = 1, GM_G16_VERIFY_MISMATCH = 2, GM_G16_VERIFY_BAD_INPUT = 3 };
+int gm_g16_verify_batch(gm_ctx* ctx, const gm_g16_vk* vk, const void* proofs_host, const void* publics_host,
+                        size_t m, uint8_t* status_out, size_t* nb_ok);
+
 /* ---- staged prover inputs --------------------------
  * The R1CS solver (constraint/bn254/solver.go:426-532) makes a, b, c final
  * level by level.  Each level (or range) can be handed over as soon as it is

@@ -27,6 +27,25 @@ int gm_test_point_op(gm_ctx* ctx, int curve, int g2, int op, const void* a_dev,
 int gm_test_fe_sqrt(gm_ctx* ctx, int curve, int kind, const void* a_dev, size_t n, void* root_dev,
                     uint8_t* exists_dev);
 
+/* The pairing's layers on their own (csrc/pairing_impl.hpp).  An Fp12 element is
+ * twelve Fp in gnark Montgomery form in gnark-crypto's E12 memory order
+ * (C0.B0.A0, C0.B0.A1, C0.B1.A0, ... C1.B2.A1); a_dev, b_dev and out_dev hold n of
+ * them, 16-byte aligned, except:
+ *   LINE_MUL  b_dev holds the line as an Fp12 element of which only the line's
+ *             three slots are read (w^0, w^1, w^3 on the D-twists; w^0, w^2, w^3
+ *             on BLS12-381): out = a times that sparse element;
+ *   MILLER    a_dev holds n gnark G1 points, b_dev n gnark G2 points (on the
+ *             curve and in the subgroup, or (0, 0)): out = the Miller values.
+ * INV sends 0 to 0.  CYC_SQR and EXP_U (a^|u|) are defined on elements of the
+ * cyclotomic subgroup only.  FINAL_EXP: out = a^(s (p^12 - 1) / r), s as in
+ * DESIGN.md section 3.11.  b_dev is read by MUL, LINE_MUL and MILLER only. */
+enum {
+  GM_TPAIR_MUL = 0, GM_TPAIR_SQR, GM_TPAIR_INV, GM_TPAIR_CONJ, GM_TPAIR_FROB1, GM_TPAIR_FROB2, GM_TPAIR_CYC_SQR,
+  GM_TPAIR_LINE_MUL, GM_TPAIR_EXP_U, GM_TPAIR_MILLER, GM_TPAIR_FINAL_EXP, GM_TPAIR_OPS
+};
+int gm_test_pairing_op(gm_ctx* ctx, int curve, int op, const void* a_dev, const void* b_dev, size_t n,
+                       void* out_dev);
+
 /* Raw-limb hooks for the lazily reduced layer (field.hpp "Lazily reduced
  * arithmetic", curve.hpp, pair_fp2.hpp).  Elements cross the boundary as the
  * internal radix-2^29 limbs: N little-endian u32 per element (N = 9, or 14 for
