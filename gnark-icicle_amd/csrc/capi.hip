@@ -19,6 +19,7 @@
 #include "plonk_session.hpp"
 #include "plonk_setup.hpp"
 #include "plonk_scs.hpp"
+#include "plonk_verify.hpp"
 #include "plonk_wires.hpp"
 #include "plonk_wires_perm.hpp"
 #include "points_check.hpp"
@@ -1456,6 +1457,94 @@ int gm_g16_verify_batch(gm_ctx* ctx, const gm_g16_vk* vk, const void* proofs_hos
   if (!proofs_host || !status_out || (vk->nb_k > 1 && !publics_host)) return refuse_null(me);
   if (m > (~size_t(0)) / (16 * fp_bytes(vk->curve))) return codec_refuse(me, "m proofs do not fit the address space");
   return g16_verify_batch(ctx, vk, proofs_host, publics_host, m, status_out, nb_ok);
+}
+
+// ---- KZG and PLONK verification (plonk_verify.hip) ---------------------------------------
+int gm_kzg_vk_upload(gm_ctx* ctx, int curve, const gm_kzg_vk_host* vk, gm_kzg_vk** out) {
+  const char* me = "gm_kzg_vk_upload";
+  if (int rc = check_curve(curve, CURVES_ALL, me)) return rc;
+  if (!ctx || !vk || !out) return refuse_null(me);
+  *out = nullptr;
+  if (!vk->g1 || !vk->g2_0 || !vk->g2_1) return refuse_null(me);
+  return kzg_vk_upload(ctx, curve, vk, out);
+}
+
+int gm_kzg_vk_free(gm_ctx* ctx, gm_kzg_vk* vk) {
+  if (!ctx || !vk) return refuse_null("gm_kzg_vk_free");
+  if (vk->ctx != ctx) return codec_refuse("gm_kzg_vk_free", "the key belongs to another context");
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  GM_HIP(hipStreamSynchronize(ctx->stream));
+  kzg_vk_release(vk);
+  return GM_OK;
+}
+
+static int kzg_verify_entry(const char* me, gm_ctx* ctx, const gm_kzg_vk* vk, const gm_kzg_openings_host* in, size_t m,
+                            bool fold, uint8_t* status_out, size_t* nb_ok) {
+  if (!ctx || !vk) return refuse_null(me);
+  if (vk->ctx != ctx) return codec_refuse(me, "the key belongs to another context");
+  if (m == 0) {
+    if (nb_ok) *nb_ok = 0;
+    return GM_OK;
+  }
+  if (!in || !status_out || !in->digests || !in->proofs || !in->points || !in->values || (fold && !in->lambda))
+    return refuse_null(me);
+  if (m > (~size_t(0)) / (16 * fp_bytes(vk->curve))) return codec_refuse(me, "m openings do not fit the address space");
+  return kzg_verify_batch(ctx, vk, in, m, kzg_verify_chunk(m, fold), fold, status_out, nb_ok);
+}
+
+int gm_kzg_verify_batch(gm_ctx* ctx, const gm_kzg_vk* vk, const gm_kzg_openings_host* openings, size_t m,
+                        uint8_t* status_out, size_t* nb_ok) {
+  return kzg_verify_entry("gm_kzg_verify_batch", ctx, vk, openings, m, false, status_out, nb_ok);
+}
+
+int gm_kzg_verify_folded(gm_ctx* ctx, const gm_kzg_vk* vk, const gm_kzg_openings_host* openings, size_t m,
+                         uint8_t* status_out) {
+  return kzg_verify_entry("gm_kzg_verify_folded", ctx, vk, openings, m, true, status_out, nullptr);
+}
+
+int gm_plonk_vk_upload(gm_ctx* ctx, int curve, const gm_plonk_vk_host* vk, gm_plonk_vk** out) {
+  const char* me = "gm_plonk_vk_upload";
+  if (int rc = check_curve(curve, CURVES_ALL, me)) return rc;
+  if (!ctx || !vk || !out) return refuse_null(me);
+  *out = nullptr;
+  if (!vk->ql || !vk->qr || !vk->qm || !vk->qo || !vk->qk || !vk->s1 || !vk->s2 || !vk->s3 || !vk->kzg_g1 ||
+      !vk->kzg_g2_0 || !vk->kzg_g2_1 || (vk->nb_bsb && (!vk->qcp || !vk->commitment_row)))
+    return refuse_null(me);
+  if (vk->n < 8 || (vk->n & (vk->n - 1))) return codec_refuse(me, "n must be a power of two, at least 8");
+  if (vk->nb_public > vk->n) return codec_refuse(me, "nb_public exceeds n");
+  if (vk->nb_bsb > 1024) return codec_refuse(me, "nb_bsb exceeds 1024");
+  for (size_t j = 0; j < vk->nb_bsb; j++)
+    if (vk->commitment_row[j] >= vk->n)
+      return codec_refuse(me, ("commitment_row[" + std::to_string(j) + "] is not below n").c_str());
+  return plonk_vk_upload(ctx, curve, vk, out);
+}
+
+int gm_plonk_vk_free(gm_ctx* ctx, gm_plonk_vk* vk) {
+  if (!ctx || !vk) return refuse_null("gm_plonk_vk_free");
+  if (vk->ctx != ctx) return codec_refuse("gm_plonk_vk_free", "the key belongs to another context");
+  gm::CtxLock g(ctx);
+  GM_HIP(hipSetDevice(ctx->device));
+  GM_HIP(hipStreamSynchronize(ctx->stream));
+  plonk_vk_release(vk);
+  return GM_OK;
+}
+
+int gm_plonk_verify_batch(gm_ctx* ctx, const gm_plonk_vk* vk, const gm_plonk_proofs_host* proofs, size_t m,
+                          uint8_t* status_out, size_t* nb_ok) {
+  const char* me = "gm_plonk_verify_batch";
+  if (!ctx || !vk) return refuse_null(me);
+  if (vk->ctx != ctx) return codec_refuse(me, "the key belongs to another context");
+  if (m == 0) {
+    if (nb_ok) *nb_ok = 0;
+    return GM_OK;
+  }
+  if (!proofs || !status_out || !proofs->points || !proofs->values || !proofs->challenges ||
+      (vk->nb_public && !proofs->publics) || (vk->nb_bsb && !proofs->hashed_cmt))
+    return refuse_null(me);
+  if (m > (~size_t(0)) / (16 * fp_bytes(vk->curve) * pv_terms(vk->nb_bsb)))
+    return codec_refuse(me, "m proofs do not fit the address space");
+  return plonk_verify_run(ctx, vk, proofs, m, plonk_verify_chunk(vk, m), status_out, nb_ok);
 }
 
 // ---- Groth16 setup: fixed-base batch multiplication (g16_setup.hip) --------------------

@@ -109,6 +109,7 @@ int finish_t(gm_ctx* ctx, const PlonkPkFixed& f, unsigned flags, gm_plonk_pk* pk
   const size_t poly_bytes = 32 * n * (gm_plonk_pk::NCANON + nb + 4);
   pk->resident_bytes = poly_bytes + msm_internal_point_bytes<C, false>() * (f.srs_canonical_len + n);
 
+  pk->lin_key_qk = (flags & GM_PLONK_PK_LIN_KEY_QK) != 0;
   if (!(flags & GM_PLONK_PK_NO_COSET_CACHE)) {
     const size_t cb = 4 * (PC_FIXED + nb) * n * 32;
     if ((rc = alloc_dev(&pk->cache, cb, "coset cache"))) return rc;
@@ -133,7 +134,7 @@ int plonk_pk_check(int curve, const PlonkPkFixed& f, unsigned flags, bool other_
     set_error("plonk pk: n must be a power of two >= 8 with 4n within the 2-adicity");
     return GM_ERR_INVALID;
   }
-  if (flags & ~GM_PLONK_PK_NO_COSET_CACHE) {
+  if (flags & ~(GM_PLONK_PK_NO_COSET_CACHE | GM_PLONK_PK_LIN_KEY_QK)) {
     set_error("plonk pk: unknown flag");
     return GM_ERR_INVALID;
   }

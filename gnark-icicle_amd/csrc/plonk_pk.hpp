@@ -20,6 +20,7 @@ struct gm_plonk_pk {
   // canonical ql qr qm qo s1 s2 s3 qcp_0 .., then Lagrange qk s1 s2 s3.
   void* polys = nullptr;
   void* cache = nullptr;  // PlonkCosetCache::base, or nullptr (GM_PLONK_PK_NO_COSET_CACHE)
+  bool lin_key_qk = false;  // GM_PLONK_PK_LIN_KEY_QK: round 4 linearises with the key's Qk, as gnark does
   size_t resident_bytes = 0, cache_bytes = 0;
   // The canonical SRS points G_0 G_1 G_2 G_n G_n+1 G_n+2 (gnark affine), copied at
   // upload: the blinding of a commitment, sum_k b_k (G_n+k - G_k), and the

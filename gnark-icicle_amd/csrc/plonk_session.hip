@@ -382,12 +382,20 @@ int round4_t(gm_plonk_session* s, const void* zeta, void* lin_affine, void* clai
   const size_t n = pk->n, nb = pk->nb_bsb;
   Arena arena(ctx);  // before the drain (StreamDrain)
   DevBuf q;          // the quotient of the opening of Z~
+  DevBuf key_qk;     // GM_PLONK_PK_LIN_KEY_QK: the key's Qk in the canonical basis
   int rc;
   if ((rc = q.alloc(arena, 32 * (n + 2)))) return rc;
+  if (pk->lin_key_qk && (rc = key_qk.alloc(arena, 32 * n))) return rc;
   StreamDrain drain{ctx};
   gm_plonk_linearize_in in;
   std::vector<const void*> qcp, pi2;
   fill_stage_in(s, &in, &qcp, &pi2);
+  if (pk->lin_key_qk) {
+    // gnark's innerComputeLinearizedPoly reads trace.Qk, not the completed copy the quotient took
+    // (prove.go:1301-1337): the public inputs reach the verifier through PI(zeta) alone
+    if ((rc = canonical_from<C>(ctx, key_qk.p, pk->lagrange(gm_plonk_pk::LAG_QK), n))) return rc;
+    in.qk = key_qk.p;
+  }
   in.h = s->h;
   in.h_rand = s->has_h_rand ? s->h_rand : nullptr;
   in.alpha = s->alpha;

@@ -1,0 +1,6 @@
+// KZG and PLONK verification, BLS12-377: the instantiations of plonk_verify_impl.hpp.
+#include "plonk_verify_impl.hpp"
+
+namespace gm {
+GM_PV_INSTANTIATE(CurveBLS12377)
+}  // namespace gm

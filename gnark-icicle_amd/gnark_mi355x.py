@@ -70,11 +70,14 @@ SYMBOLS = [
     "gm_g16_pk_check_dump",
     "gm_points_decode", "gm_points_decode_host", "gm_points_encode", "gm_g16_pk_upload_encoded",
     "gm_pairing_check", "gm_pairing_check_device", "gm_g16_vk_upload", "gm_g16_vk_free", "gm_g16_verify_batch",
+    "gm_kzg_vk_upload", "gm_kzg_vk_free", "gm_kzg_verify_batch", "gm_kzg_verify_folded", "gm_plonk_vk_upload",
+    "gm_plonk_vk_free", "gm_plonk_verify_batch",
 ]
 # test-only library (include/gnark_mi355x_testhooks.h, libgnark_mi355x_testhooks.so)
 TEST_SYMBOLS = ["gm_test_field_op", "gm_test_point_op", "gm_test_stage_replay_chain",
                 "gm_test_msm_g2_keyless_plan", "gm_test_field_raw_op", "gm_test_point_raw_op",
-                "gm_test_msm_geometry", "gm_test_scan", "gm_test_fe_sqrt", "gm_test_pairing_op"]
+                "gm_test_msm_geometry", "gm_test_scan", "gm_test_fe_sqrt", "gm_test_pairing_op",
+                "gm_test_plonk_verify_scalars", "gm_test_plonk_verify_chunked", "gm_test_kzg_verify_chunked"]
 TESTHOOKS_PATH = os.path.join(os.path.dirname(LIB_PATH), "libgnark_mi355x_testhooks.so")
 
 
@@ -127,6 +130,7 @@ class _PlonkLinearizeOut(ctypes.Structure):
 
 PLONK_PK_POLYS = ("ql", "qr", "qm", "qo", "qk", "s1", "s2", "s3")
 PLONK_PK_NO_COSET_CACHE = 1
+PLONK_PK_LIN_KEY_QK = 4
 
 
 class _PlonkPkHost(ctypes.Structure):
@@ -264,6 +268,34 @@ class _G16VkHost(ctypes.Structure):
 (TPAIR_MUL, TPAIR_SQR, TPAIR_INV, TPAIR_CONJ, TPAIR_FROB1, TPAIR_FROB2, TPAIR_CYC_SQR, TPAIR_LINE_MUL, TPAIR_EXP_U,
  TPAIR_MILLER, TPAIR_FINAL_EXP) = range(11)
 G16_VERIFY_OK, G16_VERIFY_BAD_POINT, G16_VERIFY_MISMATCH, G16_VERIFY_BAD_INPUT = 0, 1, 2, 3
+# gm_kzg_verify_batch / gm_plonk_verify_batch status bytes
+KZG_VERIFY_OK, KZG_VERIFY_BAD_POINT, KZG_VERIFY_MISMATCH, KZG_VERIFY_BAD_INPUT = 0, 1, 2, 3
+(PLONK_VERIFY_OK, PLONK_VERIFY_BAD_POINT, PLONK_VERIFY_MISMATCH, PLONK_VERIFY_BAD_INPUT,
+ PLONK_VERIFY_ALGEBRAIC) = range(5)
+
+
+class _KzgVkHost(ctypes.Structure):
+    """gm_kzg_vk_host (include/gnark_mi355x.h)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("g1", "g2_0", "g2_1")]
+
+
+class _KzgOpeningsHost(ctypes.Structure):
+    """gm_kzg_openings_host."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("digests", "proofs", "points", "values", "lambda_")]
+
+
+class _PlonkVkHost(ctypes.Structure):
+    """gm_plonk_vk_host."""
+    _fields_ = ([("n", ctypes.c_size_t), ("nb_public", ctypes.c_size_t)]
+                + [(k, ctypes.c_void_p) for k in ("ql", "qr", "qm", "qo", "qk", "s1", "s2", "s3")]
+                + [("nb_bsb", ctypes.c_size_t), ("qcp", ctypes.c_void_p),
+                   ("commitment_row", ctypes.POINTER(ctypes.c_size_t))]
+                + [(k, ctypes.c_void_p) for k in ("kzg_g1", "kzg_g2_0", "kzg_g2_1")])
+
+
+class _PlonkProofsHost(ctypes.Structure):
+    """gm_plonk_proofs_host."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("points", "values", "publics", "hashed_cmt", "challenges")]
 
 
 class _MsmGeom(ctypes.Structure):
@@ -301,6 +333,10 @@ def load_testhooks(path: str = None):
     T.gm_test_scan.argtypes = [vp, i, vp, sz, vp]
     T.gm_test_fe_sqrt.argtypes = [vp, i, i, vp, sz, vp, vp]
     T.gm_test_pairing_op.argtypes = [vp, i, i, vp, vp, sz, vp]
+    T.gm_test_plonk_verify_scalars.argtypes = [vp, vp, ctypes.POINTER(_PlonkProofsHost), sz, vp, vp, vp]
+    T.gm_test_plonk_verify_chunked.argtypes = [vp, vp, ctypes.POINTER(_PlonkProofsHost), sz, sz, vp,
+                                               ctypes.POINTER(sz)]
+    T.gm_test_kzg_verify_chunked.argtypes = [vp, vp, ctypes.POINTER(_KzgOpeningsHost), sz, sz, i, vp, ctypes.POINTER(sz)]
     _testhooks = T
     return T
 
@@ -451,6 +487,13 @@ def load_library(path: str = LIB_PATH):
     L.gm_g16_vk_upload.argtypes = [vp, i, ctypes.POINTER(_G16VkHost), pvp]
     L.gm_g16_vk_free.argtypes = [vp, vp]
     L.gm_g16_verify_batch.argtypes = [vp, vp, vp, vp, sz, vp, psz]
+    L.gm_kzg_vk_upload.argtypes = [vp, i, ctypes.POINTER(_KzgVkHost), pvp]
+    L.gm_kzg_vk_free.argtypes = [vp, vp]
+    L.gm_kzg_verify_batch.argtypes = [vp, vp, ctypes.POINTER(_KzgOpeningsHost), sz, vp, psz]
+    L.gm_kzg_verify_folded.argtypes = [vp, vp, ctypes.POINTER(_KzgOpeningsHost), sz, vp]
+    L.gm_plonk_vk_upload.argtypes = [vp, i, ctypes.POINTER(_PlonkVkHost), pvp]
+    L.gm_plonk_vk_free.argtypes = [vp, vp]
+    L.gm_plonk_verify_batch.argtypes = [vp, vp, ctypes.POINTER(_PlonkProofsHost), sz, vp, psz]
     _lib = L
     return L
 
@@ -1566,6 +1609,134 @@ class VerifyingKey:
             self.handle = None
 
 
+class KzgVk:
+    """A KZG verifying key resident on the device (gm_kzg_vk_upload): gnark point
+    bytes g1 (the G1 generator), g2_0 and g2_1 = [tau] G2."""
+
+    def __init__(self, ctx: Context, curve, g1, g2_0, g2_1):
+        self.ctx, self.curve = ctx, curve_id(curve)
+        arrs = [_buf(g1), _buf(g2_0), _buf(g2_1)]
+        host = _KzgVkHost(*[a.ctypes.data for a in arrs])
+        h = ctypes.c_void_p()
+        _check(load_library().gm_kzg_vk_upload(ctx.handle, self.curve, ctypes.byref(host), ctypes.byref(h)))
+        self.handle = h
+
+    def _openings(self, digests, proofs, points, values, lambdas=None):
+        arrs = [_buf(x) for x in (digests, proofs, points, values)] + [_buf(lambdas) if lambdas is not None else None]
+        m = arrs[2].size // FR_BYTES
+        pb = point_bytes(self.curve, False)
+        assert arrs[0].size == m * pb and arrs[1].size == m * pb and arrs[3].size == m * FR_BYTES
+        assert arrs[4] is None or arrs[4].size == m * FR_BYTES
+        return arrs, _KzgOpeningsHost(*[a.ctypes.data if a is not None and a.size else None for a in arrs]), m
+
+    def verify_batch(self, digests, proofs, points, values, per_chunk=None) -> tuple[np.ndarray, int]:
+        """gm_kzg_verify_batch: m openings (digest C, proof H, point z, value y);
+        (status bytes, accepted).  per_chunk: through the test hook, that many
+        openings per chunk."""
+        keep, host, m = self._openings(digests, proofs, points, values)
+        st = np.full(max(m, 1), 0xEE, np.uint8)
+        nb_ok = ctypes.c_size_t(0)
+        if per_chunk is None:
+            _check(load_library().gm_kzg_verify_batch(self.ctx.handle, self.handle, ctypes.byref(host), m, _p(st),
+                                                      ctypes.byref(nb_ok)))
+        else:
+            _check(load_testhooks().gm_test_kzg_verify_chunked(self.ctx.handle, self.handle, ctypes.byref(host), m,
+                                                               per_chunk, 0, _p(st), ctypes.byref(nb_ok)))
+        return st[:m], int(nb_ok.value)
+
+    def verify_folded(self, digests, proofs, points, values, lambdas, per_chunk=None) -> int:
+        """gm_kzg_verify_folded: the m openings folded with the caller's lambdas
+        (lambda_0 is taken as 1) into one product; the batch's status byte."""
+        keep, host, m = self._openings(digests, proofs, points, values, lambdas)
+        st = np.full(1, 0xEE, np.uint8)
+        if per_chunk is None:
+            _check(load_library().gm_kzg_verify_folded(self.ctx.handle, self.handle, ctypes.byref(host), m, _p(st)))
+        else:
+            _check(load_testhooks().gm_test_kzg_verify_chunked(self.ctx.handle, self.handle, ctypes.byref(host), m,
+                                                               per_chunk, 1, _p(st), None))
+        return int(st[0])
+
+    def free(self):
+        if self.handle:
+            _check(load_library().gm_kzg_vk_free(self.ctx.handle, self.handle))
+            self.handle = None
+
+
+class PlonkVk:
+    """A PLONK verifying key resident on the device (gm_plonk_vk_upload).  vk: n,
+    nb_public, gnark G1 point bytes ql, qr, qm, qo, qk, s1, s2, s3, qcp (nb_bsb points,
+    one after the other), commitment_row (absolute rows) and the KZG members kzg_g1,
+    kzg_g2_0, kzg_g2_1."""
+    POINTS = ("ql", "qr", "qm", "qo", "qk", "s1", "s2", "s3")
+
+    def __init__(self, ctx: Context, curve, vk: dict):
+        self.ctx, self.curve = ctx, curve_id(curve)
+        arrs = {k: _buf(vk[k]) for k in self.POINTS + ("kzg_g1", "kzg_g2_0", "kzg_g2_1")}
+        qcp = _buf(vk.get("qcp", b""))
+        rows = (ctypes.c_size_t * max(len(vk.get("commitment_row", ())), 1))(*vk.get("commitment_row", ()))
+        self.nb_bsb = qcp.size // point_bytes(curve, False)
+        self.n, self.nb_public = int(vk["n"]), int(vk["nb_public"])
+        host = _PlonkVkHost(self.n, self.nb_public, *[arrs[k].ctypes.data for k in self.POINTS], self.nb_bsb,
+                            qcp.ctypes.data if qcp.size else None, rows if self.nb_bsb else None,
+                            *[arrs[k].ctypes.data for k in ("kzg_g1", "kzg_g2_0", "kzg_g2_1")])
+        h = ctypes.c_void_p()
+        _check(load_library().gm_plonk_vk_upload(ctx.handle, self.curve, ctypes.byref(host), ctypes.byref(h)))
+        self.handle = h
+
+    def _proofs(self, points, values, publics, hashed_cmt, challenges):
+        arrs = [_buf(x if x is not None else b"") for x in (points, values, publics, hashed_cmt, challenges)]
+        m = arrs[4].size // (6 * FR_BYTES)
+        assert arrs[0].size == m * (9 + self.nb_bsb) * point_bytes(self.curve, False)
+        assert arrs[1].size == m * (7 + self.nb_bsb) * FR_BYTES and arrs[2].size == m * self.nb_public * FR_BYTES
+        assert arrs[3].size == m * self.nb_bsb * FR_BYTES
+        return arrs, _PlonkProofsHost(*[a.ctypes.data if a.size else None for a in arrs]), m
+
+    def verify_batch(self, points, values, publics, hashed_cmt, challenges, per_chunk=None) -> tuple[np.ndarray, int]:
+        """gm_plonk_verify_batch: m proofs, each array holding the proofs' parts one
+        after the other (the header has the order); (status bytes, accepted).
+        per_chunk: through the test hook, that many proofs per chunk."""
+        keep, host, m = self._proofs(points, values, publics, hashed_cmt, challenges)
+        st = np.full(max(m, 1), 0xEE, np.uint8)
+        nb_ok = ctypes.c_size_t(0)
+        if per_chunk is None:
+            _check(load_library().gm_plonk_verify_batch(self.ctx.handle, self.handle, ctypes.byref(host), m, _p(st),
+                                                        ctypes.byref(nb_ok)))
+        else:
+            _check(load_testhooks().gm_test_plonk_verify_chunked(self.ctx.handle, self.handle, ctypes.byref(host), m,
+                                                                 per_chunk, _p(st), ctypes.byref(nb_ok)))
+        return st[:m], int(nb_ok.value)
+
+    def test_scalars(self, values, publics, hashed_cmt, challenges):
+        """gm_test_plonk_verify_scalars: (scalars bytes, m x (18 + 2 nb_bsb) Fr; aux
+        bytes, m x (PI(zeta), constLin); class bytes)."""
+        m = _buf(challenges).size // (6 * FR_BYTES)
+        pts = np.zeros(m * (9 + self.nb_bsb) * point_bytes(self.curve, False), np.uint8)
+        keep, host, m = self._proofs(pts, values, publics, hashed_cmt, challenges)
+        T = 18 + 2 * self.nb_bsb
+        scal, aux = np.zeros(m * T * FR_BYTES, np.uint8), np.zeros(m * 2 * FR_BYTES, np.uint8)
+        cls = np.full(m, 0xEE, np.uint8)
+        _check(load_testhooks().gm_test_plonk_verify_scalars(self.ctx.handle, self.handle, ctypes.byref(host), m,
+                                                             _p(scal), _p(aux), _p(cls)))
+        return scal.tobytes(), aux.tobytes(), cls
+
+    def free(self):
+        if self.handle:
+            _check(load_library().gm_plonk_vk_free(self.ctx.handle, self.handle))
+            self.handle = None
+
+
+def kzg_vk_upload(ctx: Context, curve, g1, g2_0, g2_1) -> KzgVk:
+    return KzgVk(ctx, curve, g1, g2_0, g2_1)
+
+
+def kzg_verify_batch(vk: KzgVk, digests, proofs, points, values) -> tuple[np.ndarray, int]:
+    return vk.verify_batch(digests, proofs, points, values)
+
+
+def plonk_vk_upload(ctx: Context, curve, vk: dict) -> PlonkVk:
+    return PlonkVk(ctx, curve, vk)
+
+
 class PendingMsm:
     def __init__(self, handle, curve, g2):
         self.handle, self.curve, self.g2 = handle, curve, g2
@@ -1645,12 +1816,15 @@ class PlonkProvingKey:
     host bytes keyed by PLONK_PK_POLYS (n elements each, Lagrange regular; qk
     without public inputs and commitment values); qcp: list of host bytes;
     commitment_row: their rows of Qk; srs_canonical / srs_lagrange: gnark G1Affine
-    bytes.  cache=False uploads with GM_PLONK_PK_NO_COSET_CACHE.  A None among
+    bytes.  cache=False uploads with GM_PLONK_PK_NO_COSET_CACHE; lin_key_qk=True with
+    GM_PLONK_PK_LIN_KEY_QK (round 4 linearises with the key's Qk: the proofs a gnark
+    verifier and PlonkVk.verify_batch accept).  A None among
     the inputs passes a NULL pointer; srs_canonical_len overrides the length
     taken from the bytes."""
 
     def __init__(self, ctx: Context, curve, n: int, nb_public: int, polys: dict, qcp, commitment_row,
-                 srs_canonical, srs_lagrange, cache: bool = True, srs_canonical_len: int | None = None):
+                 srs_canonical, srs_lagrange, cache: bool = True, srs_canonical_len: int | None = None,
+                 lin_key_qk: bool = False):
         self.ctx, self.curve, self.n, self.nb_public = ctx, curve, n, nb_public
         self.nb_bsb = len(qcp) if qcp is not None else len(commitment_row or [])
         h = _PlonkPkHost()
@@ -1679,13 +1853,14 @@ class PlonkProvingKey:
             if srs_canonical_len is None else srs_canonical_len
         out = ctypes.c_void_p()
         _check(load_library().gm_plonk_pk_upload(ctx.handle, curve_id(curve), ctypes.byref(h),
-                                                 0 if cache else PLONK_PK_NO_COSET_CACHE, ctypes.byref(out)))
+                                                 (0 if cache else PLONK_PK_NO_COSET_CACHE)
+                                                 | (PLONK_PK_LIN_KEY_QK if lin_key_qk else 0), ctypes.byref(out)))
         self.handle = out
 
     @classmethod
     def setup(cls, ctx: Context, curve, n: int, nb_public: int, polys: dict, permutation, qcp, commitment_row,
               srs_canonical, cache: bool = True, srs_canonical_len: int | None = None, lagrange: bool = False,
-              digests: bool = True, wires: "PlonkWires | None" = None):
+              digests: bool = True, wires: "PlonkWires | None" = None, lin_key_qk: bool = False):
         """The key from what gnark's Setup holds (gm_plonk_pk_setup): polys keyed by
         PLONK_SETUP_POLYS, permutation = trace.S (3n integers), the canonical SRS
         alone.  Returns (key, the 8 + nb_bsb digests S1 S2 S3 Ql Qr Qm Qo Qk Qcp_j as
@@ -1728,7 +1903,7 @@ class PlonkProvingKey:
         dig = np.zeros(pb * (8 + self.nb_bsb), np.uint8) if digests else None
         lag = np.zeros(pb * n, np.uint8) if lagrange else None
         out = ctypes.c_void_p()
-        flags = 0 if cache else PLONK_PK_NO_COSET_CACHE
+        flags = (0 if cache else PLONK_PK_NO_COSET_CACHE) | (PLONK_PK_LIN_KEY_QK if lin_key_qk else 0)
         tail = (ctypes.byref(out), _p(dig) if digests else None, _p(lag) if lagrange else None)
         if wires is None:
             _check(load_library().gm_plonk_pk_setup(ctx.handle, curve_id(curve), ctypes.byref(h), flags, *tail))

@@ -413,6 +413,17 @@ typedef struct {
   const void* srs_lagrange;        /* gnark G1Affine, n points */
 } gm_plonk_pk_host;
 #define GM_PLONK_PK_NO_COSET_CACHE 1u
+/* Round 4 of a session on this key builds the linearised polynomial from the key's
+ * qk, as gnark's innerComputeLinearizedPoly does (prove.go:1301-1337 reads trace.Qk;
+ * the completed Qk serves the quotient alone), so that lin, its claimed value and the
+ * batch opening are the ones gnark's Verify and gm_plonk_verify_batch accept.  Without
+ * the flag round 4 takes the completed Qk, the behaviour of this entry before the
+ * flag existed: those proofs are refused by a gnark verifier (errAlgebraicRelation)
+ * whenever a public input or a commitment value is non-zero, and are kept only so
+ * that bytes recorded earlier stay reproducible.  One more inverse transform of n
+ * elements per proof; the same flag is taken by every entry that makes a gm_plonk_pk.
+ * Bit 2u is not assigned and stays refused as an unknown flag. */
+#define GM_PLONK_PK_LIN_KEY_QK 4u
 int gm_plonk_pk_upload(gm_ctx* ctx, int curve, const gm_plonk_pk_host* pk, unsigned flags, gm_plonk_pk** out);
 int gm_plonk_pk_bytes(const gm_plonk_pk* pk, size_t* resident_bytes, size_t* coset_cache_bytes);
 int gm_plonk_pk_free(gm_ctx* ctx, gm_plonk_pk* pk);
@@ -449,7 +460,9 @@ int gm_plonk_pk_free(gm_ctx* ctx, gm_plonk_pk* pk);
  *    the canonical SRS; with h_rand = (rho0, rho1) those of h1 || rho0, of h2
  *    with [0] -= rho0 followed by rho1, and of h3 with [0] -= rho1.
  *  - round 4 (:600-617, :656-724): the linearized polynomial as gm_plonk_linearize
- *    defines it, from zeta; lin_affine = its commit; claimed receives, in the
+ *    defines it, from zeta, over the completed Qk or, on a key made with
+ *    GM_PLONK_PK_LIN_KEY_QK, over the key's qk as gnark does (see the flag: only
+ *    those proofs pass gnark's Verify); lin_affine = its commit; claimed receives, in the
  *    order of polysToOpen (:736-744), lin(zeta), l~(zeta), r~(zeta), o~(zeta),
  *    s1(zeta), s2(zeta), qcp_j(zeta) (6 + nb_bsb elements): what the caller derives
  *    the folding challenge from; z_shifted_value = z~(w zeta) and
@@ -1156,6 +1169,119 @@ int gm_g16_vk_free(gm_ctx* ctx, gm_g16_vk* vk);
 enum { GM_G16_VERIFY_OK = 0, GM_G16_VERIFY_BAD_POINT = 1, GM_G16_VERIFY_MISMATCH = 2, GM_G16_VERIFY_BAD_INPUT = 3 };
 int gm_g16_verify_batch(gm_ctx* ctx, const gm_g16_vk* vk, const void* proofs_host, const void* publics_host,
                         size_t m, uint8_t* status_out, size_t* nb_ok);
+
+/* ---- KZG and PLONK verification, batched -----------------
+ * What gnark's plonk.Verify computes after its transcript (backend/plonk/bn254/
+ * verify.go:128-322, with gnark-crypto's kzg.FoldProof and
+ * kzg.BatchVerifyMultiPoints), and kzg.Verify, on the pairing above.  The
+ * Fiat-Shamir transcript and hash-to-field stay with the caller: challenges and
+ * the hashed BSB22 commitments enter as Montgomery fr.Elements.  Every point is a
+ * gnark G1Affine or G2Affine, every scalar a Montgomery fr.Element, all in host
+ * memory; the arrays are streamed in chunks of whole openings or proofs and no
+ * host pointer is kept.  The decisions are gnark's; no intermediate point is
+ * returned.  A status byte is, first that applies,
+ *   BAD_POINT   a point of the opening or proof failed the point check,
+ *   BAD_INPUT   an Fr word string is not below r, or a multiplier that must not
+ *               be zero is (u; lambda_i for i > 0: a zero drops an opening),
+ *   ALGEBRAIC   PLONK only: constLin != ClaimedValues[0], gnark's errAlgebraicRelation,
+ *   MISMATCH    the pairing equation fails,
+ * else OK, with gm_g16_verify_batch's values.  A bad opening or proof never fails
+ * the call.
+ *
+ * A KZG verifying key: G1 generator, G2[0], G2[1] = [tau] G2.  The upload runs the
+ * point check on each and refuses the key with GM_ERR_INVALID, naming the member
+ * and the class, if one fails; G, G2[0] and -G2[1] stay on the device.  Free the
+ * key before gm_destroy.
+ *
+ * gm_kzg_verify_batch: m independent openings, opening i = digest C_i, proof H_i,
+ * point z_i, claimed value y_i:  status_out[i] from
+ *   e(C - [y] G + [z] H, G2[0]) e(H, -G2[1]) == 1
+ * (two ladders, two Miller lanes and one final exponentiation per opening);
+ * *nb_ok (may be NULL) counts the accepted ones.  openings->lambda is not read.
+ * gm_kzg_verify_folded: kzg.BatchVerifyMultiPoints' folded form.  The caller
+ * supplies m random lambda_i; lambda_0 is not read and taken as 1, as gnark-crypto
+ * does.  One product of two pairs for the batch,
+ *   e(sum lambda_i (C_i - [y_i] G + [z_i] H_i), G2[0]) e(sum lambda_i H_i, -G2[1]) == 1,
+ * and one byte: status_out[0].  BAD_POINT or BAD_INPUT of any opening is the
+ * batch's.
+ * GM_ERR_INVALID: a NULL context, key, struct, array or status_out, a key of
+ * another context, an unknown curve id.  m == 0: GM_OK with nothing written. */
+enum { GM_KZG_VERIFY_OK = 0, GM_KZG_VERIFY_BAD_POINT = 1, GM_KZG_VERIFY_MISMATCH = 2, GM_KZG_VERIFY_BAD_INPUT = 3 };
+typedef struct gm_kzg_vk gm_kzg_vk;
+typedef struct {
+  const void *g1, *g2_0, *g2_1;
+} gm_kzg_vk_host;
+typedef struct {
+  const void* digests; /* m G1Affine */
+  const void* proofs;  /* m G1Affine: OpeningProof.H */
+  const void* points;  /* m Fr: z */
+  const void* values;  /* m Fr: OpeningProof.ClaimedValue */
+  const void* lambda;  /* m Fr, the folded form only */
+} gm_kzg_openings_host;
+int gm_kzg_vk_upload(gm_ctx* ctx, int curve, const gm_kzg_vk_host* vk, gm_kzg_vk** out);
+int gm_kzg_vk_free(gm_ctx* ctx, gm_kzg_vk* vk);
+int gm_kzg_verify_batch(gm_ctx* ctx, const gm_kzg_vk* vk, const gm_kzg_openings_host* openings, size_t m,
+                        uint8_t* status_out, size_t* nb_ok);
+int gm_kzg_verify_folded(gm_ctx* ctx, const gm_kzg_vk* vk, const gm_kzg_openings_host* openings, size_t m,
+                         uint8_t* status_out /* one byte */);
+
+/* A PLONK verifying key resident on the device: n (a power of two >= 8, the
+ * proving key's), nb_public, the digests Ql, Qr, Qm, Qo, Qk, S1, S2, S3, nb_bsb
+ * digests Qcp (one array) with commitment_row[j], the absolute rows as
+ * gm_plonk_pk_host gives them (gnark's NbPublicVariables +
+ * CommitmentConstraintIndexes[j]), and the three KZG members.  The upload runs
+ * the point check on every point and refuses the key naming the member and the
+ * class; it derives 1 / n, the generator w of the domain, the coset shift
+ * (FrMultiplicativeGen) and w^row[j] once and keeps -G2[1].  Free the key before
+ * gm_destroy.  GM_ERR_INVALID, with a message and nothing left allocated: a NULL
+ * argument or member, an unknown curve id, n not a power of two or < 8 or beyond
+ * the field's two-adicity, nb_public > n, nb_bsb > 1024, nb_bsb > 0 with a NULL
+ * qcp or commitment_row, a commitment_row >= n. */
+typedef struct gm_plonk_vk gm_plonk_vk;
+typedef struct {
+  size_t n, nb_public;
+  const void *ql, *qr, *qm, *qo, *qk, *s1, *s2, *s3; /* one G1Affine each */
+  size_t nb_bsb;
+  const void* qcp;              /* nb_bsb G1Affine */
+  const size_t* commitment_row; /* nb_bsb */
+  const void *kzg_g1, *kzg_g2_0, *kzg_g2_1;
+} gm_plonk_vk_host;
+int gm_plonk_vk_upload(gm_ctx* ctx, int curve, const gm_plonk_vk_host* vk, gm_plonk_vk** out);
+int gm_plonk_vk_free(gm_ctx* ctx, gm_plonk_vk* vk);
+/* m proofs against one key in the same launches.  Per proof,
+ *   points      9 + nb_bsb G1Affine: L, R, O, Z, H0, H1, H2, BatchedProof.H,
+ *               ZShiftedOpening.H, Bsb22Commitments[j];
+ *   values      7 + nb_bsb Fr: BatchedProof.ClaimedValues in polysToOpen order (lin,
+ *               l, r, o, s1, s2, qcp_j), then ZShiftedOpening.ClaimedValue: the order
+ *               gm_plonk_session_round4 returns them;
+ *   publics     nb_public Fr (may be NULL when nb_public == 0);
+ *   hashed_cmt  nb_bsb Fr, the caller's hash-to-field of each Bsb22 commitment (may
+ *               be NULL when nb_bsb == 0);
+ *   challenges  6 Fr: gamma, beta, alpha, zeta, v (FoldProof's folding challenge) and
+ *               u (the random multiplier of the second opening in
+ *               BatchVerifyMultiPoints; u = 0 is BAD_INPUT);
+ * each array holding the m proofs' parts one after the other.  Per proof one lane
+ * computes zeta^n, L1(zeta), PI(zeta) (the nb_public + nb_bsb + 1 denominators
+ * inverted together, zeros left zero), constLin and the 18 + 2 nb_bsb scalars;
+ * one lane per (proof, scalar) runs a double-and-add ladder; one lane per proof
+ * adds the terms into A and B = Hb + [u] Hz, and e(A, G2[0]) e(B, -G2[1]) == 1 is
+ * checked with two Miller lanes and one final exponentiation.  status_out[i] is
+ * GM_PLONK_VERIFY_*; *nb_ok (may be NULL) counts the accepted proofs.  The
+ * workspace of a call grows with nb_public (one Fr per proof of a chunk and
+ * denominator).  GM_ERR_INVALID: a NULL context, key, struct, required array or
+ * status_out, a key of another context.  m == 0: GM_OK with nothing written. */
+enum {
+  GM_PLONK_VERIFY_OK = 0,
+  GM_PLONK_VERIFY_BAD_POINT = 1,
+  GM_PLONK_VERIFY_MISMATCH = 2,
+  GM_PLONK_VERIFY_BAD_INPUT = 3,
+  GM_PLONK_VERIFY_ALGEBRAIC = 4
+};
+typedef struct {
+  const void *points, *values, *publics, *hashed_cmt, *challenges;
+} gm_plonk_proofs_host;
+int gm_plonk_verify_batch(gm_ctx* ctx, const gm_plonk_vk* vk, const gm_plonk_proofs_host* proofs, size_t m,
+                          uint8_t* status_out, size_t* nb_ok);
 
 /* ---- staged prover inputs --------------------------
  * The R1CS solver (constraint/bn254/solver.go:426-532) makes a, b, c final

@@ -155,6 +155,24 @@ typedef struct gm_test_msm_geom {
 } gm_test_msm_geom;
 int gm_test_msm_geometry(int curve, int g2, size_t n, int c_override, int layout, gm_test_msm_geom* out);
 
+/* The scalars kernel of gm_plonk_verify_batch alone (the proofs' points are not
+ * read): per proof the 18 + 2 nb_bsb scalars in the order of the ladders
+ *   G, Ql, Qr, Qm, Qo, S3, S1, S2, Qcp_j; L, R, O, Z, H0, H1, H2, Hb, Hz, Bsb_j; u
+ * to scalars_out, PI(zeta) and constLin to aux_out (2 per proof), all Montgomery
+ * fr.Elements, and to class_out the proof's class without the points:
+ * GM_PLONK_VERIFY_OK, _BAD_INPUT or _ALGEBRAIC.  One chunk: m is small. */
+int gm_test_plonk_verify_scalars(gm_ctx* ctx, const gm_plonk_vk* vk, const gm_plonk_proofs_host* proofs, size_t m,
+                                 void* scalars_out, void* aux_out, uint8_t* class_out);
+/* gm_plonk_verify_batch with per_chunk whole proofs per chunk instead of the
+ * computed count. */
+int gm_test_plonk_verify_chunked(gm_ctx* ctx, const gm_plonk_vk* vk, const gm_plonk_proofs_host* proofs, size_t m,
+                                 size_t per_chunk, uint8_t* status_out, size_t* nb_ok);
+/* The KZG entries with per_chunk whole openings per chunk: fold == 0 is
+ * gm_kzg_verify_batch, fold != 0 is gm_kzg_verify_folded, which writes one status
+ * byte and sets *nb_ok to 0 or 1. */
+int gm_test_kzg_verify_chunked(gm_ctx* ctx, const gm_kzg_vk* vk, const gm_kzg_openings_host* openings, size_t m,
+                               size_t per_chunk, int fold, uint8_t* status_out, size_t* nb_ok);
+
 #ifdef __cplusplus
 }
 #endif
